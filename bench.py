@@ -10,6 +10,12 @@ before timing; H2D copies are not part of any timed number.
 
 Default workload = BASELINE configs[1]: C2 'foo|bar|baz' over 16 GiB synthetic
 ASCII words on 1 MI355X.
+
+A plain run sets up, warms up, times the steps and prints the result line.
+--full adds the legs that take runs of their own (one rank only): the
+PCIe-inclusive host-buffer rate, the reference CPU baseline and the parity of
+its sample with the GPU scan.  --dump-outputs DIR writes what the last timed
+step returned as DIR/<name>.npy (float64; see dump_outputs).
 """
 import argparse
 import json
@@ -201,6 +207,59 @@ def pcie_inclusive(pat, buf, nbytes, dev, reps=3):
             "equals_device_resident": ok}
 
 
+DUMP_RECORDS = 1 << 20  # --dump-outputs: records kept of a longer list (3 arrays x 8 B each: 24 MiB)
+
+
+def _halves(v):
+    """A u64 as two exact float64 values (high and low 32 bits)."""
+    return np.array([v >> 32, v & 0xFFFFFFFF], dtype=np.float64)
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the last timed step returned to its caller, one
+    float64 array per file under `path`:
+
+      count.npy              [matches]
+      digest.npy, dcap.npy   the u64 sums as [high 32 bits, low 32 bits]
+      exit.npy               [the FIND chain's exit position]
+      records_start.npy, records_len.npy, records_accept.npy (--offsets only;
+                             accept only for 16-byte records): the records
+                             this rank holds, in chain order; of more than
+                             DUMP_RECORDS records, the ones at DUMP_RECORDS
+                             sorted positions drawn with a fixed seed
+                             (records_index.npy holds the positions)
+
+    The corpus and the pattern depend on the arguments alone, so two builds
+    run with the same arguments write comparable files."""
+    os.makedirs(path, exist_ok=True)
+    out = {"count": np.array([res["count"]], dtype=np.float64), "digest": _halves(res["digest"]),
+           "dcap": _halves(res["dcap"]), "exit": np.array([res["exit"]], dtype=np.float64)}
+    if "records" in res:
+        sts, lns, acs, _ = res["records"]
+        sizes = [int(s_.numel()) for s_ in sts]
+        n = sum(sizes)
+        idx = np.arange(n, dtype=np.int64)
+        if n > DUMP_RECORDS:
+            idx = np.sort(np.random.default_rng(20240607).integers(0, n, size=DUMP_RECORDS, dtype=np.int64))
+            out["records_index"] = idx.astype(np.float64)
+        base = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+
+        def pick(parts):
+            got = []
+            for i, p in enumerate(parts):
+                sel = idx[(idx >= base[i]) & (idx < base[i + 1])] - base[i]
+                got.append(p[torch.from_numpy(sel).to(p.device)].cpu().numpy().astype(np.float64))
+            return np.concatenate(got) if got else np.zeros(0, np.float64)
+
+        out["records_start"] = pick(sts)
+        out["records_len"] = pick(lns)
+        if all(a is not None for a in acs):
+            out["records_accept"] = pick(acs)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+    log("outputs written to %s: %s" % (path, ", ".join(sorted(out))))
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -251,10 +310,16 @@ def main():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--bytes", type=int, default=0, help="bytes per GPU (default: the config's size)")
     ap.add_argument("--halo", type=int, default=1 << 20, help="readable bytes past a shard end")
-    ap.add_argument("--cpu-sample-mib", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own (one rank only): "
+                         "the PCIe-inclusive host-buffer rate, the reference CPU baseline and its parity sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (count, digest, dcap, exit; with --offsets "
+                         "the match records) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-sample-mib", type=int, default=4096, help="--full: sample of the CPU baseline leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--pcie-sample-mib", type=int, default=2048,
-                    help="host-buffer sample for the PCIe-inclusive leg (0 = skip)")
+                    help="--full: host-buffer sample for the PCIe-inclusive leg (0 = skip)")
     ap.add_argument("--offsets-exchange", choices=("auto", "gather", "sharded"), default="auto",
                     help="N>1 --offsets: gather the records to rank 0 (SURVEY 8e step 4), keep them on their ranks "
                          "and exchange only their sums (dist.verify_sharded), or auto: gather when all records "
@@ -278,6 +343,8 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="bring the ranks up (process group, all_gather, barrier) and report them; no GPU work")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # rehearsal knobs for a one-GPU box: UGPU_BENCH_BACKEND=gloo puts every rank
     # on UGPU_BENCH_DEVICE (default 0) and stitches over gloo on the host
@@ -468,12 +535,14 @@ def main():
         e = torch.tensor([elapsed], dtype=torch.float64, device=xdev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
     pcie = None
     buf = shard.buf  # (a grown halo replaced it)
-    if rank == 0 and world == 1 and args.pcie_sample_mib > 0:
+    if args.full and rank == 0 and world == 1 and args.pcie_sample_mib > 0:
         pcie = pcie_inclusive(pat, buf, min(args.pcie_sample_mib << 20, hi - lo), dev)
     cpu_leg = (None, None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # value: the reference on one GPU's share of the node's cores (the
         # visible CPUs / 8 GPUs of an MI355X node, at least 16); also reported:
         # the same on every visible core (os.sched_getaffinity shows the whole
