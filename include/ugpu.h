@@ -398,6 +398,36 @@ int ugpu_stream_reserve(const ugpu_dfa *dfa, int n, uint64_t feed_bytes);
 int ugpu_lines(const uint8_t *dbuf, uint64_t len, const uint64_t *d_start, uint64_t n, uint64_t *d_line,
                uint64_t *newlines, uint64_t *matching_lines, void *stream);
 
+/* --- line records (the bol/eol half) ---
+   Same buffer rules as ugpu_lines.  Line k (1-based) is the bytes after the
+   (k-1)-th '\n' up to and including the k-th; a non-empty tail after the last
+   '\n' is a last, unterminated line; an empty buffer has no lines.  A line
+   record is (begin, end, lineno): begin = offset of the line's first byte
+   (matcher->bol()), end = offset of its '\n', or len for the unterminated
+   line (matcher->eol(true) without the newline).
+
+   ugpu_select_lines replaces the line loop of src/ugrep.cpp:11432-11521 for a
+   sorted match list (d_len NULL: all lengths 0): a match (s, l) with s < len
+   touches every line from the one holding byte s through the one holding byte
+   min(max(s, s+l-1), len-1); a match starting on a '\n' belongs to the line
+   that newline ends; matches with s >= len are ignored.  The touched lines
+   (with UGPU_SEL_INVERT, ugrep -v: the untouched ones) are written once each,
+   ascending, to d_begin/d_end/d_lineno (all three NULL: count only).
+   *lines = number of lines, *selected = number of selected lines; when that
+   exceeds capacity the call returns UGPU_CAPACITY with *selected valid and
+   writes no record.  Synchronous. */
+#define UGPU_SEL_INVERT 1u
+int ugpu_select_lines(const uint8_t *dbuf, uint64_t len, const uint64_t *d_start, const uint32_t *d_len, uint64_t n,
+                      uint32_t flags, uint64_t *d_begin, uint64_t *d_end, uint64_t *d_lineno, uint64_t capacity,
+                      uint64_t *selected, uint64_t *lines, void *stream);
+
+/* (begin, end) of each line of an ascending device list of line numbers
+   (repeats allowed), e.g. the context lines around a selection, a --range, or
+   the d_line of ugpu_lines: matcher->bol() / eol(true) by line number.  Line 0
+   or a line past the last gives UINT64_MAX in both fields.  Synchronous. */
+int ugpu_line_spans(const uint8_t *dbuf, uint64_t len, const uint64_t *d_lineno, uint64_t n, uint64_t *d_begin,
+                    uint64_t *d_end, void *stream);
+
 /* --- binary-file detection ---
    Device buffers of any alignment (the kernel reads the enclosing 16-byte
    granules).  Synchronous. */

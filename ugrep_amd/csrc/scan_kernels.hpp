@@ -304,6 +304,42 @@ hipError_t launch_nl_count(const LinesParams& L, bool sparse, hipStream_t stream
 hipError_t launch_nl_assign(const LinesParams& L, bool sparse, hipStream_t stream);
 uint32_t lines_tile();
 constexpr uint32_t kLinesQuarter = 1024;
+// line records, linesel.hip: the same wave ranges; per-wave arrays stitched on
+// the host between the passes
+struct SelParams {
+  const uint8_t* g;         // 16-byte aligned buffer
+  uint64_t len;             // bytes
+  uint64_t per;             // bytes per wave range (multiple of 4 KiB)
+  uint64_t nwaves;
+  const uint64_t* starts;   // sorted match starts
+  const uint32_t* lens;     // match lengths (NULL: all zero)
+  uint64_t nmatch;
+  uint32_t invert;          // select the lines no match touches
+  uint64_t* lastnl;         // out (summary pass): 1 + position of the range's last '\n' (0: none)
+  uint64_t* mcover;         // out (summary pass): largest exclusive end of the matches starting in the range
+  const uint64_t* prefix;   // in: newlines before each wave range
+  const uint64_t* bol;      // in: begin of the line holding the range's first byte
+  const uint64_t* cover;    // in: largest exclusive end of the matches starting before the range
+  const uint64_t* obase;    // in (write pass): index of the wave's first record
+  uint64_t* selcnt;         // out (count pass): selected lines ending in the range
+  uint64_t* begin;          // out (write pass): the records
+  uint64_t* end;
+  uint64_t* lineno;
+};
+struct SpanParams {
+  const uint8_t* g;
+  uint64_t len, per, nwaves;
+  const uint64_t* q;        // ascending line numbers (1-based; repeats allowed)
+  uint64_t nq;
+  const uint64_t* counts;   // newlines per wave range
+  const uint64_t* prefix;   // newlines before each wave range
+  uint64_t newlines;
+  uint64_t* begin;          // out: UINT64_MAX in both for a line that does not exist
+  uint64_t* end;
+};
+hipError_t launch_sel_summary(const SelParams& S, hipStream_t stream);
+hipError_t launch_sel(const SelParams& S, bool write, hipStream_t stream);
+hipError_t launch_spans(const SpanParams& Q, hipStream_t stream);
 // binary-file detection, utf8.hip: first byte failing reflex::isutf8 (or, with
 // nul, the first 0x00) of the data bytes [head, head + len) of the 16-byte
 // aligned span g[0, span), atomically min'ed into *out (preset to ~0)

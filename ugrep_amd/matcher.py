@@ -12,6 +12,7 @@ ugrep worker consumes matches from a mmap'd file (src/ugrep.cpp:3936-3940,
 CPU fallback in this module: tables the engine does not support raise
 `Unsupported`, as ugpu_dfa_create returns UGPU_UNSUPPORTED.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -522,6 +523,111 @@ def lines(dptr, length, d_start=0, n=0, d_line=0, stream=0):
     check(lib.ugpu_lines(ctypes.c_void_p(dptr), length, ctypes.c_void_p(d_start), n, ctypes.c_void_p(d_line),
                          ctypes.byref(nl), ctypes.byref(ml), ctypes.c_void_p(stream)))
     return nl.value, ml.value
+
+
+def select_lines(dptr, length, d_start, d_len, n, invert=False, d_begin=0, d_end=0, d_lineno=0, capacity=0,
+                 stream=0):
+    """ugpu_select_lines over a 16-byte aligned device buffer and its sorted
+    device match list (d_len 0: zero-length matches): (selected, lines).  The
+    records (begin, end, lineno) of the lines the matches touch (invert: of the
+    others) go to the three device arrays of `capacity` elements (all 0: count
+    only).  Too small a capacity raises UgpuError with code UGPU_CAPACITY and
+    the counts in its .selected / .lines."""
+    sel = ctypes.c_uint64()
+    nl = ctypes.c_uint64()
+    rc = lib.ugpu_select_lines(ctypes.c_void_p(dptr), length, ctypes.c_void_p(d_start or None),
+                               ctypes.c_void_p(d_len or None), n, _lib.SEL_INVERT if invert else 0,
+                               ctypes.c_void_p(d_begin or None), ctypes.c_void_p(d_end or None),
+                               ctypes.c_void_p(d_lineno or None), capacity, ctypes.byref(sel), ctypes.byref(nl),
+                               ctypes.c_void_p(stream))
+    if rc == _lib.UGPU_CAPACITY:
+        err = _lib.UgpuError(rc, lib.ugpu_last_error().decode(errors="replace"))
+        err.selected, err.lines = sel.value, nl.value
+        raise err
+    check(rc)
+    return sel.value, nl.value
+
+
+def line_spans(dptr, length, d_lineno, n, d_begin, d_end, stream=0):
+    """ugpu_line_spans: d_begin[i], d_end[i] = byte span (newline excluded) of
+    line d_lineno[i] of an ascending device list; 2^64-1 in both for a line
+    that does not exist."""
+    check(lib.ugpu_line_spans(ctypes.c_void_p(dptr), length, ctypes.c_void_p(d_lineno or None), n,
+                              ctypes.c_void_p(d_begin or None), ctypes.c_void_p(d_end or None),
+                              ctypes.c_void_p(stream)))
+
+
+def context_lines(selected_lineno, nlines, before, after):
+    """The lines ugrep prints for -B before -A after around the selected lines
+    (ascending, 1-based) of an input of nlines lines: (lineno, kind), merged and
+    ascending, kind 1 = selected, 0 = context; context is clipped to the input."""
+    sel = np.asarray(selected_lineno, dtype=np.int64)
+    if sel.size == 0:
+        return np.zeros(0, np.uint64), np.zeros(0, np.uint8)
+    lo = np.maximum(sel - int(before), 1)
+    hi = np.minimum(sel + int(after), int(nlines))
+    new = np.ones(sel.size, bool)  # a group begins where the window leaves a gap behind the previous one
+    new[1:] = lo[1:] > hi[:-1] + 1
+    first = np.flatnonzero(new)
+    glo = lo[first]
+    ghi = hi[np.append(first[1:] - 1, sel.size - 1)]
+    cnt = ghi - glo + 1
+    off = np.cumsum(cnt) - cnt
+    lineno = np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(off, cnt) + np.repeat(glo, cnt)
+    at = np.searchsorted(sel, lineno)
+    kind = (sel[np.minimum(at, sel.size - 1)] == lineno).astype(np.uint8)
+    return lineno.astype(np.uint64), kind
+
+
+LineResult = collections.namedtuple("LineResult", "lineno begin end kind")
+
+
+def grep_lines(pattern, data, invert=False, before=0, after=0):
+    """The lines `ugrep -n [-v] [-B before] [-A after]` prints for one input:
+    LineResult(lineno, begin, end, kind) numpy arrays, ascending; data[begin:end]
+    is the line without its newline, kind 1 = selected, 0 = context.  Composes
+    find_all, select_lines, context_lines and, for the context lines only,
+    line_spans; the line work runs on the current device."""
+    import torch
+    ptr, n, keep = _buffer_ptr(data)
+    if n == 0:  # an empty input has no lines
+        return LineResult(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64),
+                          np.zeros(0, np.uint8))
+    if hasattr(keep, "is_cuda") and keep.is_cuda and not ptr & 15:
+        dev = keep.view(torch.uint8).reshape(-1)
+    else:  # (granule loads: 16-byte aligned, readable to the end of the last granule)
+        dev = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+        if n:
+            src = keep if hasattr(keep, "data_ptr") else torch.from_numpy(keep if keep.flags.writeable else keep.copy())
+            dev[:n].copy_(src.view(torch.uint8).reshape(-1))
+    r = find_all(pattern, dev[:n], offsets=True)
+    m = int(r.count)
+    d_start = torch.from_numpy(r.start.astype(np.int64)).to(dev.device)
+    d_len = torch.from_numpy(r.length.astype(np.int32)).to(dev.device)
+    torch.cuda.synchronize()
+    sel, nlines = select_lines(dev.data_ptr(), n, d_start.data_ptr(), d_len.data_ptr(), m, invert)
+    rec = torch.zeros((3, max(sel, 1)), dtype=torch.int64, device=dev.device)
+    torch.cuda.synchronize()
+    select_lines(dev.data_ptr(), n, d_start.data_ptr(), d_len.data_ptr(), m, invert, rec[0].data_ptr(),
+                 rec[1].data_ptr(), rec[2].data_ptr(), sel)
+    begin, end, lineno = (a.astype(np.uint64) for a in rec[:, :sel].cpu().numpy())
+    kind = np.ones(sel, np.uint8)
+    if (before or after) and sel:
+        lineno_all, kind = context_lines(lineno, nlines, before, after)
+        ctx = kind == 0
+        nctx = int(ctx.sum())
+        b_all = np.empty(lineno_all.size, np.uint64)
+        e_all = np.empty(lineno_all.size, np.uint64)
+        b_all[~ctx], e_all[~ctx] = begin, end
+        if nctx:
+            q = torch.from_numpy(lineno_all[ctx].astype(np.int64)).to(dev.device)
+            sp = torch.zeros((2, nctx), dtype=torch.int64, device=dev.device)
+            torch.cuda.synchronize()
+            line_spans(dev.data_ptr(), n, q.data_ptr(), nctx, sp[0].data_ptr(), sp[1].data_ptr())
+            b_all[ctx], e_all[ctx] = (a.astype(np.uint64) for a in sp.cpu().numpy())
+        lineno, begin, end = lineno_all, b_all, e_all
+    del keep
+    return LineResult(lineno, begin, end, kind)
 
 
 def check_utf8(dptr, length, stream=0):
