@@ -92,6 +92,8 @@ typedef struct ugpu_dfa_info
 #define UGPU_SHAPE_LOOKAHEAD 16u /* lookahead (X(?=Y): TAIL/HEAD words): the lookahead walk on wfind_kernel */
 #define UGPU_SHAPE_LOOP_NEEDLE 8u /* C+ N on the sparse kernel: the prefilter looks for the needle N and walks back
                                      (UGPU_LB=0 disables) */
+#define UGPU_SHAPE_FILTER2 32u /* the sparse kernel's prefilter tests two of a byte's three bit fields: it adds few
+                                  candidates for this table (UGPU_FT2=0 / 1 forces it) */
 
 /* Totals of one scan.  digest = sum(start*31 + len), dcap = sum((start+1)*cap),
    both mod 2^64, start = byte offset + bias. */

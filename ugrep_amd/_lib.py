@@ -20,6 +20,7 @@ UGPU_HALO = 5
 UGPU_CAPACITY = 6
 
 SHAPE_FINITE, SHAPE_WORD_COND, SHAPE_ONE_ACCEPT, SHAPE_LOOP_NEEDLE, SHAPE_LOOKAHEAD = 1, 2, 4, 8, 16
+SHAPE_FILTER2 = 32
 
 MODE_COUNT = 0
 MODE_OFFSETS = 1

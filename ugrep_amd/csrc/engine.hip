@@ -324,6 +324,7 @@ void fill_tables(ScanParams& P, const ugpu_dfa* d)
   P.amap = P.ctx_word ? d->d_acap + d->t.acap_rows.size() : nullptr;
   P.nul = d->nul ? 1u : 0u;
   P.wstart = d->wstart && env_u64("UGPU_WSTART", 1) != 0 ? 1u : 0u;
+  P.ft2 = plan_filter2(d->t, d->plan) ? 1u : 0u;  // (UGPU_FT2 forces it)
   P.bol0 = 1;
   // chain bytes one stitch merge may cross before the chains count as not
   // resynchronising (two chains of a resynchronising table meet within a match

@@ -294,6 +294,13 @@ DfaPlan dfa_plan(const DfaTables& t, uint32_t flags, int lb)
   return p;
 }
 
+bool plan_filter2(const DfaTables& t, const DfaPlan& p)
+{
+  if (!t.filter || t.format != FMT_BYTE || p.lb || p.amode || p.wtab) return false;
+  const char* env = std::getenv("UGPU_FT2");
+  return env && env[0] ? env[0] != '0' : t.filter2;
+}
+
 void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* out)
 {
   ugpu_dfa_info* info = static_cast<ugpu_dfa_info*>(out);
@@ -309,7 +316,7 @@ void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* out)
   info->contexts = t.ctx_word ? 64u : t.anchored ? 4u : 1u;
   info->shape = (t.finite ? UGPU_SHAPE_FINITE : 0u) | (t.word_cond_edges ? UGPU_SHAPE_WORD_COND : 0u) |
                 (t.cap1 != 0 && !t.anchored ? UGPU_SHAPE_ONE_ACCEPT : 0u) | (p.lb ? UGPU_SHAPE_LOOP_NEEDLE : 0u) |
-                (t.lookahead ? UGPU_SHAPE_LOOKAHEAD : 0u);
+                (t.lookahead ? UGPU_SHAPE_LOOKAHEAD : 0u) | (plan_filter2(t, p) ? UGPU_SHAPE_FILTER2 : 0u);
   const char* xenv = std::getenv("UGPU_XI");
   const char* genv = std::getenv("UGPU_XG");
   const char* cenv = std::getenv("UGPU_XC");
@@ -375,7 +382,8 @@ int ugpu_tables_build_host(const uint32_t* opc, uint32_t nop, ugpu_dfa_info* inf
   info->accepting = t.accepting;
   info->contexts = t.ctx_word ? 64u : t.anchored ? 4u : 1u;
   info->shape = (t.finite ? UGPU_SHAPE_FINITE : 0u) | (t.word_cond_edges ? UGPU_SHAPE_WORD_COND : 0u) |
-                (t.cap1 != 0 && !t.anchored ? UGPU_SHAPE_ONE_ACCEPT : 0u);
+                (t.cap1 != 0 && !t.anchored ? UGPU_SHAPE_ONE_ACCEPT : 0u) |
+                (plan_filter2(t, dfa_plan(t, 0)) ? UGPU_SHAPE_FILTER2 : 0u);
   info->kernel = (t.filter && t.format == FMT_BYTE) ? 0u
                  : t.format == FMT_WIDE              ? 4u
                  : (t.xc && t.cap1 != 0)             ? 5u

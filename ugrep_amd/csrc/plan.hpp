@@ -46,6 +46,10 @@ struct DfaPlan {
 
 // lb: loop-needle lookback 1 / 0, or -1 for the UGPU_LB default (on)
 DfaPlan dfa_plan(const DfaTables& t, uint32_t flags, int lb = -1);
+// The two-field prefilter (tables.hpp filter2) on the plain sparse path: a
+// first-byte prefilter walked by the plain walk (no loop needle, option W or
+// context accepts).  UGPU_FT2=0 / 1, read per call, forces it off / on there.
+bool plan_filter2(const DfaTables& t, const DfaPlan& p);
 // ugpu_dfa_info from the tables and the plan (ugpu_dfa_plan_host, ugpu_dfa_info_get)
 void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* info /* ugpu_dfa_info* */);
 // \w+ as ugpu_compile builds it

@@ -215,6 +215,9 @@ struct ScanParams {
   // at the match begin, lib/matcher.cpp:107; or a table whose every accept
   // needs CTX_WB), so candidates right after an ASCII letter are dropped
   uint32_t wstart;
+  // sparse_kernel, plain walks on a first-byte prefilter: the prefilter tests
+  // the lo3 and mid3 fields only (tables.hpp filter2; UGPU_FT2 forces it)
+  uint32_t ft2;
   // sparse_kernel, loop-needle tables (engine.hip loop_needle): the prefilter
   // (ft) finds the needle N; each candidate walks back over the bytes of C
   // (256-bit mask) to its run's start.  NULL: ft finds first bytes.

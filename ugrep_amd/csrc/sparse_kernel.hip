@@ -45,14 +45,20 @@ namespace {
 // byte-table lookups on the lo3 / mid3 / hi2 fields of every byte, ANDed.
 // Byte i of the result holds B_g(i) at bit g, C_g(i) at bit 2+g, D_g(i) at
 // bit 4+g; bits 6 and 7 are 0.
+// FT2 (ScanParams::ft2): the hi2 lookup is left out.  It only tells a byte
+// from its aliases in the other 64-byte quadrants (`f` from `&`), so without
+// it the result is a superset (r0 & r1 still has bits 6 and 7 clear) and every
+// candidate is walked exactly: one shift, one AND and one v_perm less per dword.
 struct FTab {
   uint32_t t0lo, t0hi, t1lo, t1hi, t2;
 };
 
+template <bool FT2>
 __device__ __forceinline__ uint32_t bucket_bits(uint32_t x, const FTab& F)
 {
   const uint32_t r0 = __builtin_amdgcn_perm(F.t0hi, F.t0lo, x & 0x07070707u);
   const uint32_t r1 = __builtin_amdgcn_perm(F.t1hi, F.t1lo, (x >> 3) & 0x07070707u);
+  if constexpr (FT2) return r0 & r1;
   const uint32_t r2 = __builtin_amdgcn_perm(F.t2, F.t2, (x >> 6) & 0x03030303u);
   return r0 & r1 & r2;
 }
@@ -677,7 +683,8 @@ __device__ __forceinline__ void flush_deferred(const uint64_t* dl, uint8_t* scr,
 // by the wave's range [wlo, whi).
 // ABL (benchmarking only; results are not matches): 1 loads alone, 2 loads +
 // prefilter, 3 everything but the walks.
-template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool RESUME = false, bool LB = false>
+template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool RESUME = false, bool LB = false,
+          bool FT2 = false>
 __device__ __forceinline__ void tile_pass(const uint4& v0, const uint4& v1, const uint4& v2, const uint4& v3,
                                           uint64_t ts, bool edge, uint64_t wlo, uint64_t whi, int lane,
                                           const FTab& F, const Tab<0>& T, const Ctx& C, const ScanParams& P,
@@ -691,8 +698,8 @@ __device__ __forceinline__ void tile_pass(const uint4& v0, const uint4& v1, cons
   // the 4 bytes after chunk k of a lane are the next lane's first dword
   // (DPP wave_shl:1), or lane 0's of chunk k+1 for lane 63; past the tile
   // they are unknown and pass
-  const uint32_t h0 = bucket_bits(v0.x, F), h1 = bucket_bits(v1.x, F), h2 = bucket_bits(v2.x, F),
-                 h3 = bucket_bits(v3.x, F);
+  const uint32_t h0 = bucket_bits<FT2>(v0.x, F), h1 = bucket_bits<FT2>(v1.x, F), h2 = bucket_bits<FT2>(v2.x, F),
+                 h3 = bucket_bits<FT2>(v3.x, F);
   // (the DPP moves must run with every lane enabled -- a disabled source lane
   // reads as 0 -- so they are computed unconditionally, then selected)
   const uint32_t n0 = __builtin_amdgcn_update_dpp(0, h0, 0x130, 0xf, 0xf, false);
@@ -705,28 +712,28 @@ __device__ __forceinline__ void tile_pass(const uint4& v0, const uint4& v1, cons
   const uint32_t e0 = l63 ? s1 : n0, e1 = l63 ? s2 : n1, e2 = l63 ? s3 : n2, e3 = l63 ? 0x3f3f3f3fu : n3;
   uint32_t X[4][4];
   {
-    const uint32_t y = bucket_bits(v0.y, F), z = bucket_bits(v0.z, F), u = bucket_bits(v0.w, F);
+    const uint32_t y = bucket_bits<FT2>(v0.y, F), z = bucket_bits<FT2>(v0.z, F), u = bucket_bits<FT2>(v0.w, F);
     X[0][0] = cand_flags(h0, y);
     X[0][1] = cand_flags(y, z);
     X[0][2] = cand_flags(z, u);
     X[0][3] = cand_flags(u, e0);
   }
   {
-    const uint32_t y = bucket_bits(v1.y, F), z = bucket_bits(v1.z, F), u = bucket_bits(v1.w, F);
+    const uint32_t y = bucket_bits<FT2>(v1.y, F), z = bucket_bits<FT2>(v1.z, F), u = bucket_bits<FT2>(v1.w, F);
     X[1][0] = cand_flags(h1, y);
     X[1][1] = cand_flags(y, z);
     X[1][2] = cand_flags(z, u);
     X[1][3] = cand_flags(u, e1);
   }
   {
-    const uint32_t y = bucket_bits(v2.y, F), z = bucket_bits(v2.z, F), u = bucket_bits(v2.w, F);
+    const uint32_t y = bucket_bits<FT2>(v2.y, F), z = bucket_bits<FT2>(v2.z, F), u = bucket_bits<FT2>(v2.w, F);
     X[2][0] = cand_flags(h2, y);
     X[2][1] = cand_flags(y, z);
     X[2][2] = cand_flags(z, u);
     X[2][3] = cand_flags(u, e2);
   }
   {
-    const uint32_t y = bucket_bits(v3.y, F), z = bucket_bits(v3.z, F), u = bucket_bits(v3.w, F);
+    const uint32_t y = bucket_bits<FT2>(v3.y, F), z = bucket_bits<FT2>(v3.z, F), u = bucket_bits<FT2>(v3.w, F);
     X[3][0] = cand_flags(h3, y);
     X[3][1] = cand_flags(y, z);
     X[3][2] = cand_flags(z, u);
@@ -824,7 +831,8 @@ __device__ __forceinline__ TileLoad wave_tile(const uint8_t* wbase, uint32_t i, 
 
 }  // namespace
 
-template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool RESUME = false, bool LB = false>
+template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool RESUME = false, bool LB = false,
+          bool FT2 = false>
 __global__ __launch_bounds__(kSpWaves * 64, RESUME ? 1 : (W == kWalkCtx ? UGPU_SP_CTX_OCC : 6)) void sparse_kernel(ScanParams P)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -969,8 +977,8 @@ __global__ __launch_bounds__(kSpWaves * 64, RESUME ? 1 : (W == kWalkCtx ? UGPU_S
   // rest of its range without processing it); an odd last tile follows
   if (n >= i + 2) {
     do {
-      tile_pass<WRITE, ABL, W, STAGE, RESUME, LB>(a0, a1, a2, a3, wb + (uint64_t)i * kWaveTile, i == 0 && clip_lo, wlo, whi,
-                                              lane, F, T, C, P, dl, scr, w, lim, gw);
+      tile_pass<WRITE, ABL, W, STAGE, RESUME, LB, FT2>(a0, a1, a2, a3, wb + (uint64_t)i * kWaveTile, i == 0 && clip_lo,
+                                                       wlo, whi, lane, F, T, C, P, dl, scr, w, lim, gw);
       {
         const TileLoad L = wave_tile(wbase, i + 2, rel);
         a0 = stream16(L, lo16);
@@ -978,8 +986,9 @@ __global__ __launch_bounds__(kSpWaves * 64, RESUME ? 1 : (W == kWalkCtx ? UGPU_S
         a2 = stream16(L, lo16 + 2048);
         a3 = stream16(L, lo16 + 3072);
       }
-      tile_pass<WRITE, ABL, W, STAGE, RESUME, LB>(b0, b1, b2, b3, wb + (uint64_t)(i + 1) * kWaveTile, i + 2 == n && clip_hi,
-                                              wlo, whi, lane, F, T, C, P, dl, scr, w, lim, gw);
+      tile_pass<WRITE, ABL, W, STAGE, RESUME, LB, FT2>(b0, b1, b2, b3, wb + (uint64_t)(i + 1) * kWaveTile,
+                                                       i + 2 == n && clip_hi, wlo, whi, lane, F, T, C, P, dl, scr, w,
+                                                       lim, gw);
       {
         const TileLoad L = wave_tile(wbase, i + 3, rel);
         b0 = stream16(L, lo16);
@@ -991,9 +1000,9 @@ __global__ __launch_bounds__(kSpWaves * 64, RESUME ? 1 : (W == kWalkCtx ? UGPU_S
     } while (i + 1 < n);
   }
   if (i < n)  // a* holds tile i = n - 1
-    tile_pass<WRITE, ABL, W, STAGE, RESUME, LB>(a0, a1, a2, a3, wb + (uint64_t)i * kWaveTile,
-                                            (i == 0 && clip_lo) || clip_hi, wlo, whi, lane, F, T, C, P, dl, scr, w,
-                                            lim, gw);
+    tile_pass<WRITE, ABL, W, STAGE, RESUME, LB, FT2>(a0, a1, a2, a3, wb + (uint64_t)i * kWaveTile,
+                                                     (i == 0 && clip_lo) || clip_hi, wlo, whi, lane, F, T, C, P, dl,
+                                                     scr, w, lim, gw);
   if constexpr (LB) {
     // loop-needle tables: the C-run that reaches the range end is this wave's
     // candidate (its needles may all lie in the next waves' ranges)
@@ -1089,29 +1098,31 @@ size_t sparse_smem_bytes(uint32_t ntrans_pad, uint32_t nstates, uint32_t nlds_ac
 
 namespace {
 
-template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool RESUME = false, bool LB = false>
+template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool RESUME = false, bool LB = false,
+          bool FT2 = false>
 hipError_t sparse_launch(const ScanParams& P, size_t smem, hipStream_t stream)
 {
   static size_t attr_smem = 65536;
   if (smem > attr_smem) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_kernel<WRITE, ABL, W, STAGE, RESUME, LB>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    hipError_t e =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_kernel<WRITE, ABL, W, STAGE, RESUME, LB, FT2>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     if (e != hipSuccess) return e;
     attr_smem = smem;
   }
-  hipLaunchKernelGGL((sparse_kernel<WRITE, ABL, W, STAGE, RESUME, LB>), dim3(P.grid), dim3(kSpWaves * 64), smem, stream,
-                     P);
+  hipLaunchKernelGGL((sparse_kernel<WRITE, ABL, W, STAGE, RESUME, LB, FT2>), dim3(P.grid), dim3(kSpWaves * 64), smem,
+                     stream, P);
   return hipGetLastError();
 }
 
 // The main launch, then (plain walks) the resume launch for the waves it
 // suspended at long walks.
-template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool LB = false>
+template <bool WRITE, int ABL, int W = kWalkPlain, bool STAGE = false, bool LB = false, bool FT2 = false>
 hipError_t sparse_one(const ScanParams& P, size_t smem, hipStream_t stream)
 {
-  hipError_t e = sparse_launch<WRITE, ABL, W, STAGE, false, LB>(P, smem, stream);
+  hipError_t e = sparse_launch<WRITE, ABL, W, STAGE, false, LB, FT2>(P, smem, stream);
   if constexpr (W == kWalkPlain && ABL == 0) {
-    if (e == hipSuccess && P.susp) e = sparse_launch<WRITE, 0, kWalkPlain, STAGE, true, LB>(P, smem, stream);
+    if (e == hipSuccess && P.susp) e = sparse_launch<WRITE, 0, kWalkPlain, STAGE, true, LB, FT2>(P, smem, stream);
   }
   return e;
 }
@@ -1178,8 +1189,18 @@ hipError_t launch_sparse(const ScanParams& P, bool write, size_t smem, hipStream
     return P.st_n ? sparse_one<false, 0, kWalkWord, true>(P, smem, stream)
                   : sparse_one<false, 0, kWalkWord>(P, smem, stream);
   }
+  if (P.ft2) {  // (the plain walk's two-field prefilter: bucket_bits<true>)
+    if (write) return sparse_one<true, 0, kWalkPlain, false, false, true>(P, smem, stream);
+    if (P.st_n) return sparse_one<false, 0, kWalkPlain, true, false, true>(P, smem, stream);
+    switch (P.ablate) {  // (1: the loads alone, no filter)
+      case 1: return sparse_one<false, 1>(P, smem, stream);
+      case 2: return sparse_one<false, 2, kWalkPlain, false, false, true>(P, smem, stream);
+      case 3: return sparse_one<false, 3, kWalkPlain, false, false, true>(P, smem, stream);
+      default: return sparse_one<false, 0, kWalkPlain, false, false, true>(P, smem, stream);
+    }
+  }
   if (write) return sparse_one<true, 0>(P, smem, stream);
-  if (P.st_n) return sparse_one<false, 0, false, true>(P, smem, stream);
+  if (P.st_n) return sparse_one<false, 0, kWalkPlain, true>(P, smem, stream);
   switch (P.ablate) {  // benchmarking knob (UGPU_ABLATE): count pass only
     case 1: return sparse_one<false, 1>(P, smem, stream);
     case 2: return sparse_one<false, 2>(P, smem, stream);

@@ -75,6 +75,8 @@ struct Bucket {
     hi |= (uint8_t)(1u << (b >> 6));
   }
   bool has(int b) const { return (lo >> (b & 7) & 1) && (mid >> ((b >> 3) & 7) & 1) && (hi >> (b >> 6) & 1); }
+  // (the two-field form, tables.hpp filter2: hi is not tested)
+  bool has2(int b) const { return (lo >> (b & 7) & 1) && (mid >> ((b >> 3) & 7) & 1); }
   static Bucket all()
   {
     Bucket x;
@@ -96,6 +98,25 @@ struct Bucket {
     for (int b = 0x20; b < 0x7f; ++b) n += has(b) ? 1 : 0;
     return n / 96.0;
   }
+  double text_frac2() const
+  {
+    int n = has2('\n') ? 1 : 0;
+    for (int b = 0x20; b < 0x7f; ++b) n += has2(b) ? 1 : 0;
+    return n / 96.0;
+  }
+  // fraction of all 256 byte values in the approximation (uniform bytes)
+  double byte_frac() const
+  {
+    int n = 0;
+    for (int b = 0; b < 256; ++b) n += has(b) ? 1 : 0;
+    return n / 256.0;
+  }
+  double byte_frac2() const
+  {
+    int n = 0;
+    for (int b = 0; b < 256; ++b) n += has2(b) ? 1 : 0;
+    return n / 256.0;
+  }
 };
 
 // First bytes of a term group with the bytes that may follow them.
@@ -109,6 +130,9 @@ struct Lead {
     return *this;
   }
   double density() const { return b.text_frac() * c.text_frac() * d.text_frac(); }
+  double density2() const { return b.text_frac2() * c.text_frac2() * d.text_frac2(); }
+  double udensity() const { return b.byte_frac() * c.byte_frac() * d.byte_frac(); }
+  double udensity2() const { return b.byte_frac2() * c.byte_frac2() * d.byte_frac2(); }
 };
 
 // Partition the leads (one per first byte) into the two prefilter groups,
@@ -1118,6 +1142,14 @@ int build_tables(const uint32_t* opc, uint32_t nop, DfaTables& out, std::string&
   // the sparse kernel pays off when few positions survive the prefilter
   // (a start state that accepts: empty matches anywhere, no candidate filter)
   t.filter = t.format == FMT_BYTE && !leads.empty() && t.fdensity <= 0.15 && start_sid < first_acc;
+  // the two-field form of the same two groups (tables.hpp filter2): the
+  // candidates it adds, on text and on uniform bytes, against kFilter2Added
+  // (tables.hpp; from profiles/prefilter_fields_summary.json)
+  const double d3 = g[0].density() + g[1].density();
+  t.fdensity2 = std::min(1.0, g[0].density2() + g[1].density2());
+  t.udensity = std::min(1.0, g[0].udensity() + g[1].udensity());
+  t.udensity2 = std::min(1.0, g[0].udensity2() + g[1].udensity2());
+  t.filter2 = t.filter && t.fdensity2 - std::min(1.0, d3) <= kFilter2Added && t.udensity2 - t.udensity <= kFilter2Added;
   if (look) {
     // lookahead tables: a match end can move back to a HEAD position, which
     // none of the transducer forms or the candidate walks model; they take the

@@ -49,6 +49,14 @@ struct DfaTables {
   bool filter = false;       // false: dense pattern, no prefilter
   uint8_t ft[20] = {};       // T0[8], T1[8], T2[4]
   double fdensity = 1.0;     // estimated candidate fraction on printable ASCII
+  // Two-field form (sparse_kernel.hip bucket_bits<true>): the T2 lookup is left
+  // out, R(b) = T0[b & 7] & T1[(b >> 3) & 7], so a byte also passes for its
+  // aliases in the other 64-byte quadrants (`f` and `&`).  Still a superset;
+  // chosen when it adds few candidates (kFilter2Added) both on text and on
+  // uniformly distributed bytes.  ft and fdensity stay the three-field ones.
+  bool filter2 = false;
+  double fdensity2 = 1.0;    // two-field candidate fraction on text
+  double udensity = 1.0, udensity2 = 1.0;  // three- / two-field fraction on uniform bytes
   uint32_t first_bytes = 0;
   std::vector<uint16_t> trans;  // states * row (FMT_BYTE, FMT_CLASS)
   std::vector<uint32_t> trans32;  // states * row (FMT_WIDE)
@@ -185,6 +193,15 @@ struct DfaTables {
 constexpr uint8_t XU_SLOW = 0x0F, XU_L3 = 0x80, XU_MIX = 0x80, XU_CLS = 0x70;
 constexpr uint32_t kXuCls = 256 + 64 * 256;               // continuation classes, 256 bytes
 constexpr uint32_t kXuTab = kXuCls + 256, kXuBm3 = 2048;
+
+// Largest candidate density the two-field prefilter may add to the three-field
+// one (filter2 above), under the text model and under the uniform one.
+// Measured (tools/bench_prefilter_fields.py, profiles/prefilter_fields_summary.json):
+// with alias trigrams planted in the C2 corpus the two-field kernel is the
+// faster one up to 1e-5 added candidates per byte and no longer at 1e-4 (at
+// 1e-3 it is 12 % slower: every added candidate is walked); the bound is that
+// 1e-4 halved.  foo|bar|baz adds 2.4e-5 on text, -F lorem 9e-6.
+constexpr double kFilter2Added = 5e-5;
 
 // True when the two tables accept the same strings with the same accept
 // indices (so the FIND chains agree on every input).
