@@ -430,6 +430,62 @@ int ugpu_select_lines(const uint8_t *dbuf, uint64_t len, const uint64_t *d_start
 int ugpu_line_spans(const uint8_t *dbuf, uint64_t len, const uint64_t *d_lineno, uint64_t n, uint64_t *d_begin,
                     uint64_t *d_end, void *stream);
 
+/* --- Boolean line queries (ugrep --bool, -e A --and B --andnot C, --not, --files) ---
+   ugpu_select_lines_bool replaces the per-line CNF check of the reference
+   (cnf_matching, src/ugrep.cpp:3277-3376: one sub-matcher find() per literal
+   over every candidate line; cnf_satisfied, :3379-3427, with --files) for a
+   device-resident buffer that every sub-pattern has scanned once.
+
+   Lines, line records and "a match touches a line" are those of
+   ugpu_select_lines.  There are nlists <= UGPU_BOOL_MAX_LISTS sorted device
+   match lists (d_starts[t], d_lens[t], n[t]); d_lens NULL or d_lens[t] NULL
+   means all lengths of that list are 0; a list may be empty (n[t] == 0, its
+   pointers may be NULL).  The pointer arrays d_starts, d_lens, n and clauses
+   are host memory.  Literal t of a line is true when some match of list t
+   touches the line.  A formula is nclauses <= UGPU_BOOL_MAX_CLAUSES clauses
+   {pos, neg} over the literal bits of a line; a clause holds when
+     (bits & pos) != 0 || (~bits & neg & listmask) != 0,  listmask = 2^nlists - 1,
+   and the formula is the AND of its clauses (no clause: every line).  A mask
+   bit at or above nlists, or a clause with pos == neg == 0, gives UGPU_INVAL.
+   One clause {1, 0} over one list is ugpu_select_lines; {0, 1} is
+   ugpu_select_lines with UGPU_SEL_INVERT.
+
+   flags: UGPU_SEL_INVERT complements the selection per line.
+   UGPU_BOOL_FILES (--files) evaluates the literals over the whole input
+   (literal t is true when list t touches any line, i.e. has a match starting
+   below len); when the formula then holds, the lines touched by any list are
+   selected (the reference prints the lines of the adjoined pattern,
+   CNF::adjoin, src/cnf.cpp:736-743), otherwise none; UGPU_SEL_INVERT
+   complements that selection.  *whole (may be NULL) receives the formula's
+   truth value over the whole-input literals; without UGPU_BOOL_FILES it
+   receives whether any line is selected.
+
+   Outputs and capacity as ugpu_select_lines: all three record arrays or none
+   (count only); *selected and *lines are always valid; UGPU_CAPACITY with no
+   record written when *selected > capacity; records ascending, once per line.
+
+   The result is what ugrep --bool selects whenever no sub-pattern can match a
+   '\n' (ugpu_tables_newline_host): then "list t touches the line" is
+   "sub-matcher t finds something in [bol, eol]", and the reference's primary
+   (adjoined) pattern never removes a line the CNF accepts: it is empty when
+   every clause carries a NOT alternative (src/cnf.cpp:746-761).  For patterns
+   that can match a newline the two differ, as matching_lines of ugpu_lines
+   does.  Synchronous. */
+#define UGPU_BOOL_FILES 2u
+#define UGPU_BOOL_MAX_LISTS 16
+#define UGPU_BOOL_MAX_CLAUSES 64
+typedef struct ugpu_bool_clause { uint32_t pos, neg; } ugpu_bool_clause;
+int ugpu_select_lines_bool(const uint8_t *dbuf, uint64_t len, const uint64_t *const *d_starts,
+                           const uint32_t *const *d_lens, const uint64_t *n, uint32_t nlists,
+                           const ugpu_bool_clause *clauses, uint32_t nclauses, uint32_t flags, uint64_t *d_begin,
+                           uint64_t *d_end, uint64_t *d_lineno, uint64_t capacity, uint64_t *selected, uint64_t *lines,
+                           int *whole, void *stream);
+
+/* host-only: *nl = 1 when some match of the table can contain '\n', i.e. a
+   state reachable from the start state has a live edge on byte 0x0a (anchors
+   and word boundaries consume no byte and do not count). */
+int ugpu_tables_newline_host(const uint32_t *opc, uint32_t nop, int *nl);
+
 /* --- binary-file detection ---
    Device buffers of any alignment (the kernel reads the enclosing 16-byte
    granules).  Synchronous. */

@@ -16,6 +16,14 @@ summary, select-count and select-write passes), one count-only call and one
 inverted count-only call, in that order, so a kernel trace of the run gives
 the time of every pass (the select-count dispatches alternate plain, plain,
 inverted) beside nl_count_kernel's.
+
+--bool K times Boolean line queries (ugpu_select_lines_bool) on
+the same corpus: K match lists from K different needle patterns (three random
+three-letter words each, the first is the config's own), one CNF that uses
+every list; per step one count-only call and one call that writes the records.
+In the same run it times the K count-only ugpu_select_lines calls a caller
+needs without the fused pass (one per list; the K line lists would still have
+to be copied and combined on the host, which is not timed).
 """
 import argparse
 import json
@@ -40,6 +48,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--select", action="store_true", help="time ugpu_select_lines instead of ugpu_lines")
+    ap.add_argument("--bool", type=int, default=0, metavar="K", dest="nbool",
+                    help="time ugpu_select_lines_bool over K match lists (1..16)")
+    ap.add_argument("--out", default="", help="also write the JSON line to this file")
     args = ap.parse_args()
     pkey, kind, size = CONFIGS[args.config]
     n = args.bytes or size
@@ -50,6 +61,8 @@ def main():
     sptr = torch.cuda.current_stream(dev).cuda_stream
     buf = torch.empty(n + 16, dtype=torch.uint8, device=dev)
     ugrep_amd.gen(kind, 1, 0, buf.data_ptr(), n, sptr)
+    if args.nbool:
+        return boolean(args, dev, sptr, buf, n, opc)
     pat = ugrep_amd.Pattern(opc)
     sc = ugrep_amd.Scanner(pat)
     sc.scan(buf.data_ptr(), 0, n, n, True, 0, sptr)
@@ -131,6 +144,81 @@ def select(args, dev, sptr, buf, n, starts, lens, m):
         "ms_inverted_count_call": round(t_inv * 1e3, 4), "ms_ugpu_lines_count_call": round(t_lines * 1e3, 4),
         "GBps_input_write_call": round(n / t_write / 1e9, 1),
         "GBps_algorithmic_write_call": round(alg / t_write / 1e9, 1), "algorithmic_bytes": alg}), flush=True)
+
+
+NEEDLES = ["qux|zot|wib", "mep|dak|yol", "vug|hix|pym", "kob|raz|tew", "jid|nuf|gax", "lev|sop|cuz", "wam|biq|fyr",
+           "hod|zim|kep", "tuv|goj|nac", "pel|rix|dub", "sab|myk|vot", "cer|luh|zan", "fip|gow|jyt", "bux|dor|nim",
+           "yag|teq|hul"]
+
+
+def match_list(pat, dev, sptr, buf, n):
+    sc = ugrep_amd.Scanner(pat)
+    sc.scan(buf.data_ptr(), 0, n, n, True, 0, sptr)
+    m = sc.totals().count
+    starts = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    lens = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    caps = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    sc.offsets(starts.data_ptr(), lens.data_ptr(), caps.data_ptr(), m, sptr)
+    torch.cuda.synchronize(dev)
+    sc.close()
+    return starts, lens, m
+
+
+def boolean(args, dev, sptr, buf, n, opc):
+    k = args.nbool
+    if not 1 <= k <= 16:
+        sys.exit("--bool takes 1..16 lists")
+    pats = [ugrep_amd.Pattern(opc)] + [ugrep_amd.Pattern(ugrep_amd.compile_regex(rx)) for rx in NEEDLES[:k - 1]]
+    found = [match_list(p, dev, sptr, buf, n) for p in pats]
+    lists = [(s.data_ptr(), ln.data_ptr(), m) for s, ln, m in found]
+    # (list 0 or list 1) and, for every later list t: not t (t even), t or list 0 (t odd)
+    clauses = [(3 if k > 1 else 1, 0)] + [((1 << t | 1, 0) if t & 1 else (0, 1 << t)) for t in range(2, k)]
+    bp = buf.data_ptr()
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            out = fn()
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = fn()
+        torch.cuda.synchronize(dev)
+        return out, (time.perf_counter() - t0) / args.steps
+
+    sel, nlines, _ = ugrep_amd.select_lines_bool(bp, n, lists, clauses, stream=sptr)
+    rec = torch.empty((3, max(sel, 1)), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    cnt, t_count = timed(lambda: ugrep_amd.select_lines_bool(bp, n, lists, clauses, stream=sptr))
+    wrt, t_write = timed(lambda: ugrep_amd.select_lines_bool(bp, n, lists, clauses, False, False, rec[0].data_ptr(),
+                                                             rec[1].data_ptr(), rec[2].data_ptr(), sel, sptr))
+    fil, t_files = timed(lambda: ugrep_amd.select_lines_bool(bp, n, lists, clauses, False, True, stream=sptr))
+    sep, t_sep = timed(lambda: [ugrep_amd.select_lines(bp, n, s, ln, m, False, stream=sptr) for s, ln, m in lists])
+    # sanity (not timed): each list alone through the fused call gives select_lines' count; records ascending
+    alone = [ugrep_amd.select_lines_bool(bp, n, lists, [(1 << t, 0)], stream=sptr)[0] for t in range(k)]
+    asc = bool((rec[2, 1:sel] > rec[2, :sel - 1]).all().item()) if sel > 1 else True
+    mtot = sum(m for _, _, m in lists)
+    res = {
+        "what": "ugpu_select_lines_bool (count-only; record write; --files count-only) against K count-only "
+                "ugpu_select_lines calls",
+        "config": args.config, "bytes": n, "lists": k, "matches": [m for _, _, m in lists],
+        "clauses": [list(c) for c in clauses], "lines": nlines, "selected": sel, "selected_files": fil[0],
+        "counts_ok": cnt == wrt == (sel, nlines, sel > 0) and alone == [x[0] for x in sep]
+        and all(x[1] == nlines for x in sep) and sel <= nlines,
+        "records_ascending": asc,
+        "ms_bool_count_call": round(t_count * 1e3, 4), "ms_bool_write_call": round(t_write * 1e3, 4),
+        "ms_bool_files_count_call": round(t_files * 1e3, 4),
+        "ms_separate_count_calls": round(t_sep * 1e3, 4),
+        "separate_over_bool_count": round(t_sep / t_count, 2),
+        # buffer passes: newline count + select-count (+ select-write); each separate call is newline count + select-count
+        "bytes_read_bool_count_call": 2 * n + 2 * 12 * mtot,
+        "bytes_read_bool_write_call": 3 * n + 3 * 12 * mtot,
+        "bytes_read_separate_count_calls": 2 * n * k + 2 * 12 * mtot,
+        "bytes_written_bool_write_call": 24 * sel}
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":

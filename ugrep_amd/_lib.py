@@ -30,6 +30,8 @@ GEN_WORDS, GEN_PLANTED, GEN_CODE, GEN_UTF8 = 1, 2, 3, 4
 BIN_NULL_DATA, BIN_NUL_ONLY, BIN_INIT_WINDOW = 1, 2, 4
 
 SEL_INVERT = 1
+BOOL_FILES = 2
+BOOL_MAX_LISTS, BOOL_MAX_CLAUSES = 16, 64
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u16p = ctypes.POINTER(ctypes.c_uint16)
@@ -52,6 +54,10 @@ class Totals(ctypes.Structure):
 class Result(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("digest", ctypes.c_uint64), ("dcap", ctypes.c_uint64),
                 ("start", c_u64p), ("len", c_u32p), ("cap", c_u32p)]
+
+
+class BoolClause(ctypes.Structure):
+    _fields_ = [("pos", ctypes.c_uint32), ("neg", ctypes.c_uint32)]
 
 
 class UgpuError(RuntimeError):
@@ -136,6 +142,11 @@ def _load():
         "ugpu_select_lines": (ctypes.c_int, [V, ctypes.c_uint64, V, V, ctypes.c_uint64, ctypes.c_uint32, V, V, V,
                                              ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64), V]),
         "ugpu_line_spans": (ctypes.c_int, [V, ctypes.c_uint64, V, ctypes.c_uint64, V, V, V]),
+        "ugpu_select_lines_bool": (ctypes.c_int, [V, ctypes.c_uint64, P(V), P(V), c_u64p, ctypes.c_uint32,
+                                                  P(BoolClause), ctypes.c_uint32, ctypes.c_uint32, V, V, V,
+                                                  ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64),
+                                                  P(ctypes.c_int), V]),
+        "ugpu_tables_newline_host": (ctypes.c_int, [c_u32p, ctypes.c_uint32, P(ctypes.c_int)]),
         "ugpu_check_utf8": (ctypes.c_int, [V, ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_find_nul": (ctypes.c_int, [V, ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_is_binary": (ctypes.c_int, [V, ctypes.c_uint64, ctypes.c_uint32, P(ctypes.c_int), V]),

@@ -517,6 +517,39 @@ int ugpu_tables_context_host(const uint32_t* opc, uint32_t nop, uint32_t* acap, 
   return UGPU_OK;
 }
 
+int ugpu_tables_newline_host(const uint32_t* opc, uint32_t nop, int* nl)
+{
+  if (!nl) return fail(UGPU_INVAL, "NULL argument");
+  DfaTables t;
+  std::string err;
+  const int rc = build_tables(opc, nop, t, err);
+  if (rc != 0) return fail(rc == 1 ? UGPU_UNSUPPORTED : UGPU_INVAL, err);
+  // byte edges only: meta edges (anchors, word boundaries: option W, the
+  // per-context accepts) consume no byte and lead to accept-only states
+  auto step = [&t](uint32_t s, int c) {
+    const size_t i = (size_t)s * t.row + (t.format == FMT_BYTE ? (uint32_t)c : t.cls[c]);
+    return t.format == FMT_WIDE ? t.trans32[i] / t.row : (uint32_t)t.trans[i] / t.row;
+  };
+  std::vector<bool> seen(t.states, false);
+  std::vector<uint32_t> work(1, t.start / t.row);
+  seen[work[0]] = true;
+  *nl = 0;
+  while (!work.empty() && !*nl) {
+    const uint32_t s = work.back();
+    work.pop_back();
+    if (!s) continue;  // dead
+    if (step(s, '\n')) *nl = 1;
+    for (int c = 0; c < 256; ++c) {
+      const uint32_t to = step(s, c);
+      if (to && !seen[to]) {
+        seen[to] = true;
+        work.push_back(to);
+      }
+    }
+  }
+  return UGPU_OK;
+}
+
 int ugpu_tables_equivalent_host(const uint32_t* opc_a, uint32_t nop_a, const uint32_t* opc_b, uint32_t nop_b, int* eq)
 {
   if (!eq) return fail(UGPU_INVAL, "NULL argument");

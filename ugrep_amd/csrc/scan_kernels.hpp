@@ -343,6 +343,39 @@ struct SpanParams {
 hipError_t launch_sel_summary(const SelParams& S, hipStream_t stream);
 hipError_t launch_sel(const SelParams& S, bool write, hipStream_t stream);
 hipError_t launch_spans(const SpanParams& Q, hipStream_t stream);
+// the wave ranges of the line kernels for a buffer of len bytes (linesel.hip):
+// returns the current device, or -1 with the error recorded
+int line_wave_ranges(uint64_t len, uint64_t* per, uint64_t* nwaves);
+// Boolean line queries, linebool.hip: SelParams for up to 16 match lists and a
+// CNF over them.  The host passes only the lists the formula uses, renumbered
+// from 0, so bit t of a clause mask is list t of these arrays.
+constexpr uint32_t kBoolLists = 16, kBoolClauses = 64;
+struct BoolParams {
+  const uint8_t* g;         // 16-byte aligned buffer
+  uint64_t len;             // bytes
+  uint64_t per;             // bytes per wave range (multiple of 4 KiB)
+  uint64_t nwaves;
+  uint32_t nl;              // lists (<= kBoolLists)
+  uint32_t ncl;             // clauses (<= kBoolClauses)
+  uint32_t all;             // ~0: the AND starts true; 0: nothing is selected (no clause is read)
+  uint32_t invert;          // complement the formula per line
+  const uint64_t* starts[kBoolLists];  // sorted match starts of each list
+  const uint32_t* lens[kBoolLists];    // match lengths (NULL: all zero)
+  uint64_t nmatch[kBoolLists];
+  uint32_t pos[kBoolClauses], neg[kBoolClauses];  // clause c holds when (bits & pos[c]) | (~bits & neg[c])
+  uint64_t* lastnl;         // out (summary pass): 1 + position of the range's last '\n' (0: none)
+  uint64_t* mcover;         // out (summary pass): [t * nwaves + wave] largest exclusive end of list t's matches starting in the range
+  const uint64_t* prefix;   // in: newlines before each wave range
+  const uint64_t* bol;      // in: begin of the line holding the range's first byte
+  const uint64_t* cover;    // in: [t * nwaves + wave] largest exclusive end of list t's matches starting before the range
+  const uint64_t* obase;    // in (write pass): index of the wave's first record
+  uint64_t* selcnt;         // out (count pass): selected lines ending in the range
+  uint64_t* begin;          // out (write pass): the records
+  uint64_t* end;
+  uint64_t* lineno;
+};
+hipError_t launch_bool_summary(const BoolParams& S, hipStream_t stream);
+hipError_t launch_bool(const BoolParams& S, bool write, hipStream_t stream);
 // binary-file detection, utf8.hip: first byte failing reflex::isutf8 (or, with
 // nul, the first 0x00) of the data bytes [head, head + len) of the 16-byte
 // aligned span g[0, span), atomically min'ed into *out (preset to ~0)

@@ -591,25 +591,50 @@ def grep_lines(pattern, data, invert=False, before=0, after=0):
     import torch
     ptr, n, keep = _buffer_ptr(data)
     if n == 0:  # an empty input has no lines
-        return LineResult(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64),
-                          np.zeros(0, np.uint8))
-    if hasattr(keep, "is_cuda") and keep.is_cuda and not ptr & 15:
-        dev = keep.view(torch.uint8).reshape(-1)
-    else:  # (granule loads: 16-byte aligned, readable to the end of the last granule)
-        dev = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
-        if n:
-            src = keep if hasattr(keep, "data_ptr") else torch.from_numpy(keep if keep.flags.writeable else keep.copy())
-            dev[:n].copy_(src.view(torch.uint8).reshape(-1))
-    r = find_all(pattern, dev[:n], offsets=True)
-    m = int(r.count)
-    d_start = torch.from_numpy(r.start.astype(np.int64)).to(dev.device)
-    d_len = torch.from_numpy(r.length.astype(np.int32)).to(dev.device)
+        return _no_lines()
+    dev = _device_input(ptr, n, keep)
+    d_start, d_len, m = _device_matches(pattern, dev, n)
     torch.cuda.synchronize()
     sel, nlines = select_lines(dev.data_ptr(), n, d_start.data_ptr(), d_len.data_ptr(), m, invert)
     rec = torch.zeros((3, max(sel, 1)), dtype=torch.int64, device=dev.device)
     torch.cuda.synchronize()
     select_lines(dev.data_ptr(), n, d_start.data_ptr(), d_len.data_ptr(), m, invert, rec[0].data_ptr(),
                  rec[1].data_ptr(), rec[2].data_ptr(), sel)
+    out = _with_context(dev, n, rec, sel, nlines, before, after)
+    del keep
+    return out
+
+
+def _no_lines():
+    return LineResult(np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint64), np.zeros(0, np.uint8))
+
+
+def _device_input(ptr, n, keep):
+    """The input as a 16-byte aligned device tensor, readable to the end of its
+    last granule (the line kernels load whole granules)."""
+    import torch
+    if hasattr(keep, "is_cuda") and keep.is_cuda and not ptr & 15:
+        return keep.view(torch.uint8).reshape(-1)
+    dev = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+    if n:
+        src = keep if hasattr(keep, "data_ptr") else torch.from_numpy(keep if keep.flags.writeable else keep.copy())
+        dev[:n].copy_(src.view(torch.uint8).reshape(-1))
+    return dev
+
+
+def _device_matches(pattern, dev, n):
+    """(d_start, d_len, count): the match list of dev[:n] as device tensors."""
+    import torch
+    r = find_all(pattern, dev[:n], offsets=True)
+    d_start = torch.from_numpy(r.start.astype(np.int64)).to(dev.device)
+    d_len = torch.from_numpy(r.length.astype(np.int32)).to(dev.device)
+    return d_start, d_len, int(r.count)
+
+
+def _with_context(dev, n, rec, sel, nlines, before, after):
+    """LineResult of the `sel` records in the device tensor rec[3][>= sel]
+    (begin, end, lineno) plus their context lines (line_spans)."""
+    import torch
     begin, end, lineno = (a.astype(np.uint64) for a in rec[:, :sel].cpu().numpy())
     kind = np.ones(sel, np.uint8)
     if (before or after) and sel:
@@ -626,8 +651,305 @@ def grep_lines(pattern, data, invert=False, before=0, after=0):
             line_spans(dev.data_ptr(), n, q.data_ptr(), nctx, sp[0].data_ptr(), sp[1].data_ptr())
             b_all[ctx], e_all[ctx] = (a.astype(np.uint64) for a in sp.cpu().numpy())
         lineno, begin, end = lineno_all, b_all, e_all
-    del keep
     return LineResult(lineno, begin, end, kind)
+
+
+def select_lines_bool(dptr, length, lists, clauses, invert=False, files=False, d_begin=0, d_end=0, d_lineno=0,
+                      capacity=0, stream=0):
+    """ugpu_select_lines_bool over a 16-byte aligned device buffer:
+    (selected, lines, whole).  `lists` is a sequence of (d_start, d_len, n)
+    sorted device match lists (d_len 0: zero-length matches; an empty list may
+    have null pointers), `clauses` a sequence of (pos, neg) bit masks over
+    them: a line is selected when every clause has a pos list that touches it
+    or a neg list that does not.  files=True (--files) evaluates the lists over
+    the whole input and selects the lines any list touches when the formula
+    holds; `whole` is then the formula's value.  Records and capacity as
+    select_lines."""
+    lists = list(lists)
+    clauses = list(clauses)
+    k, nc = len(lists), len(clauses)
+    starts = (ctypes.c_void_p * max(k, 1))(*[ctypes.c_void_p(int(a[0]) or None) for a in lists])
+    lens = (ctypes.c_void_p * max(k, 1))(*[ctypes.c_void_p(int(a[1]) or None) for a in lists])
+    counts = (ctypes.c_uint64 * max(k, 1))(*[int(a[2]) for a in lists])
+    cl = (_lib.BoolClause * max(nc, 1))(*[_lib.BoolClause(int(p), int(q)) for p, q in clauses])
+    sel = ctypes.c_uint64()
+    nl = ctypes.c_uint64()
+    whole = ctypes.c_int()
+    flags = (_lib.SEL_INVERT if invert else 0) | (_lib.BOOL_FILES if files else 0)
+    rc = lib.ugpu_select_lines_bool(ctypes.c_void_p(dptr), length, starts, lens, counts, k, cl, nc, flags,
+                                    ctypes.c_void_p(d_begin or None), ctypes.c_void_p(d_end or None),
+                                    ctypes.c_void_p(d_lineno or None), capacity, ctypes.byref(sel), ctypes.byref(nl),
+                                    ctypes.byref(whole), ctypes.c_void_p(stream))
+    if rc == _lib.UGPU_CAPACITY:
+        err = _lib.UgpuError(rc, lib.ugpu_last_error().decode(errors="replace"))
+        err.selected, err.lines = sel.value, nl.value
+        raise err
+    check(rc)
+    return sel.value, nl.value, bool(whole.value)
+
+
+def host_newline(opc):
+    """ugpu_tables_newline_host: whether some match of the table can contain '\\n'."""
+    a, p = _as_u32(opc)
+    nl = ctypes.c_int()
+    check(lib.ugpu_tables_newline_host(p, len(a), ctypes.byref(nl)))
+    return bool(nl.value)
+
+
+# --- ugrep --bool queries (grammar: src/cnf.hpp:227-237) ---
+#   and  -> or { space+ [ 'AND' space+ ] or }*
+#   or   -> not { ( '|'+ | 'OR' space+ ) not }*
+#   not  -> [ '-' space* | 'NOT' space+ ] atom
+#   atom -> '(' and ')' | pattern
+# A '(' opens a group only when it is not '(?' and its ')' is followed by the
+# end, a space, '|' or ')' (so (foo|bar)? stays one pattern); a pattern runs
+# to the next space, '|' or ')' outside its own parentheses, brackets, quotes
+# and escapes; "..." is a literal (\Q...\E).
+
+def _skip_unit(s, i):
+    """Index behind the bracket list, quoted string, escape, \\Q..\\E span or
+    single character at s[i]."""
+    c = s[i]
+    if c == "[":
+        j = i + 1
+        if j < len(s) and s[j] == "^":
+            j += 1
+        if j < len(s):
+            j += 1  # a leading ] is a member
+        while j < len(s) and s[j] != "]":
+            j += 2 if s[j] == "\\" and j + 1 < len(s) else 1
+        return min(j + 1, len(s))
+    if c == '"':
+        j = i + 1
+        while j < len(s) and s[j] != '"':
+            j += 2 if s[j] == "\\" and j + 1 < len(s) else 1
+        return min(j + 1, len(s))
+    if c == "\\":
+        if s.startswith("\\Q", i):
+            j = s.find("\\E", i + 2)
+            return len(s) if j < 0 else j + 2
+        return min(i + 2, len(s))
+    return i + 1
+
+
+def _is_space(s, i):
+    return i < len(s) and s[i] in " \t\r\f\v"
+
+
+class _BoolParser:
+    def __init__(self, s):
+        if "\n" in s:
+            raise ValueError("a newline in a Boolean query is not supported")
+        self.s, self.i = s, 0
+        self.patterns = []
+
+    def space(self):
+        while _is_space(self.s, self.i):
+            self.i += 1
+
+    def word(self, w):
+        """Consume operator word w when it stands here followed by a space."""
+        if self.s.startswith(w, self.i) and _is_space(self.s, self.i + len(w)):
+            self.i += len(w)
+            self.space()
+            return True
+        return False
+
+    def parse_and(self):
+        items = []
+        self.space()
+        while self.i < len(self.s) and self.s[self.i] != ")":
+            items.append(self.parse_or())
+            self.space()
+            self.word("AND")
+        return ("and", items)
+
+    def parse_or(self):
+        items = [self.parse_not()]
+        while True:
+            j = self.i
+            self.space()
+            if self.i < len(self.s) and self.s[self.i] == "|":
+                while self.i < len(self.s) and self.s[self.i] == "|":
+                    self.i += 1
+                self.space()
+            elif not self.word("OR"):
+                self.i = j
+                return ("or", items)
+            items.append(self.parse_not())
+
+    def parse_not(self):
+        s = self.s
+        neg = False
+        if self.i < len(s) and s[self.i] == "-":
+            neg = True
+            self.i += 1
+            self.space()
+        elif self.word("NOT"):
+            neg = True
+        node = self.parse_atom()
+        return ("not", node) if neg else node
+
+    def group_end(self):
+        """Index of the ')' closing the '(' at self.i when that pair is a group, else -1."""
+        s, j, level = self.s, self.i + 1, 0
+        if s.startswith("(?", self.i):
+            return -1
+        while j < len(s):
+            if s[j] == "(":
+                level += 1
+            elif s[j] == ")":
+                if level == 0:
+                    k = j + 1
+                    return j if k == len(s) or s[k] in "|)" or _is_space(s, k) else -1
+                level -= 1
+            j = _skip_unit(s, j)
+        return -1
+
+    def parse_atom(self):
+        s = self.s
+        if self.i < len(s) and s[self.i] == "(":
+            end = self.group_end()
+            if end >= 0:
+                self.i += 1
+                node = self.parse_and()
+                if self.i != end:
+                    raise ValueError("unbalanced parentheses in Boolean query at offset %d" % self.i)
+                self.i += 1
+                if not node[1]:
+                    raise ValueError("empty group in Boolean query")
+                return node
+        out, level = "", 0
+        while self.i < len(s):
+            c = s[self.i]
+            if level == 0 and (c in "|)" or _is_space(s, self.i)):
+                break
+            j = _skip_unit(s, self.i)
+            if c == '"':
+                closed = j - 1 > self.i and s[j - 1] == '"'
+                lit = s[self.i + 1:j - 1 if closed else j].replace('\\"', '"')
+                if lit:
+                    out += "\\Q" + lit.replace("\\E", "\\E\\\\E\\Q") + "\\E"
+            else:
+                if c == "(":
+                    level += 1
+                elif c == ")":
+                    level -= 1
+                out += s[self.i:j]
+            self.i = j
+        if level:
+            raise ValueError("unbalanced parentheses in Boolean query")
+        if not out:
+            raise ValueError("empty pattern in Boolean query at offset %d" % self.i)
+        if out not in self.patterns:
+            self.patterns.append(out)
+        return ("lit", self.patterns.index(out))
+
+
+def _cnf(node, neg, limit):
+    """Clauses [(pos, neg)] of the tree `node` (complemented when neg): NOT is
+    pushed to the leaves (De Morgan), OR distributes over AND; clauses holding
+    a pattern and its complement are true and dropped, repeats are dropped."""
+    kind = node[0]
+    if kind == "lit":
+        return [(0, 1 << node[1])] if neg else [(1 << node[1], 0)]
+    if kind == "not":
+        return _cnf(node[1], not neg, limit)
+    parts = [_cnf(ch, neg, limit) for ch in node[1]]
+    out = []
+    if (kind == "and") != neg:  # a conjunction: the clauses of every part
+        for p in parts:
+            for c in p:
+                if c not in out:
+                    out.append(c)
+    else:  # a disjunction: one clause per choice of a clause from every part
+        out = [(0, 0)]
+        for p in parts:
+            nxt = []
+            for a in out:
+                for b in p:
+                    c = (a[0] | b[0], a[1] | b[1])
+                    if not (c[0] & c[1]) and c not in nxt:
+                        nxt.append(c)
+            out = nxt
+            if len(out) > 64 * limit:
+                raise ValueError("Boolean query needs more than %d clauses" % limit)
+    return out
+
+
+def parse_bool_query(query):
+    """(patterns, clauses) of a ugrep --bool query: space or AND means and, |
+    or OR means or, - or NOT means not (NOT binds tighter than OR, OR tighter
+    than AND), parentheses group, "..." is a literal.  The query is normalised
+    to CNF: `clauses` is a list of (pos, neg) bit masks over `patterns` (equal
+    pattern strings share one entry), as select_lines_bool takes them; the
+    empty query gives no clause.  ValueError for more than 16 distinct
+    patterns, more than 64 clauses, or a construct outside this grammar."""
+    p = _BoolParser(query)
+    tree = p.parse_and()
+    if p.i != len(query):
+        raise ValueError("unbalanced ')' in Boolean query at offset %d" % p.i)
+    if len(p.patterns) > _lib.BOOL_MAX_LISTS:
+        raise ValueError("Boolean query has more than %d distinct patterns" % _lib.BOOL_MAX_LISTS)
+    clauses = _cnf(tree, False, _lib.BOOL_MAX_CLAUSES)
+    if len(clauses) > _lib.BOOL_MAX_CLAUSES:
+        raise ValueError("Boolean query needs more than %d clauses" % _lib.BOOL_MAX_CLAUSES)
+    return p.patterns, clauses
+
+
+def _expand_quotes(rx):
+    r"""`rx` with every \Q...\E span written as escaped characters (the native
+    compiler has no \Q)."""
+    out, i = "", 0
+    while i < len(rx):
+        if rx.startswith("\\Q", i):
+            j = rx.find("\\E", i + 2)
+            j = len(rx) if j < 0 else j
+            out += "".join("\\" + c if c in "\\.^$*+?()[]{}|" else c for c in rx[i + 2:j])
+            i = j + 2
+        elif rx[i] == "\\" and i + 1 < len(rx):
+            out += rx[i:i + 2]
+            i += 2
+        else:
+            out += rx[i]
+            i += 1
+    return out
+
+
+def grep_bool(query_or_cnf, data, invert=False, files=False, before=0, after=0, icase=False):
+    """The lines `ugrep -n --bool QUERY [-v] [--files] [-B before] [-A after]`
+    prints for one input, as grep_lines returns them.  query_or_cnf is a --bool
+    query string (parse_bool_query) or a (patterns, clauses) pair: -e A --and B
+    --andnot C is (["A", "B", "C"], [(1, 0), (2, 0), (0, 4)]).  Every pattern is
+    compiled (compile_regex) and scanned once over the one device copy of the
+    input (find_all), then select_lines_bool picks the lines.  A pattern that
+    can match a newline raises ValueError: the per-line semantics of the
+    reference differ for it (include/ugpu.h)."""
+    import torch
+    patterns, clauses = parse_bool_query(query_or_cnf) if isinstance(query_or_cnf, str) else query_or_cnf
+    pats = []
+    for rx in patterns:
+        opc = compile_regex(_expand_quotes(rx), icase=icase)
+        if host_newline(opc):
+            raise ValueError("pattern %r can match a newline: not supported in a Boolean line query" % (rx,))
+        pats.append(Pattern(opc))
+    ptr, n, keep = _buffer_ptr(data)
+    if n == 0:  # an empty input has no lines
+        return _no_lines()
+    dev = _device_input(ptr, n, keep)
+    found = [_device_matches(p, dev, n) for p in pats]
+    lists = [(s.data_ptr() if m else 0, ln.data_ptr() if m else 0, m) for s, ln, m in found]
+    # without a pattern the reference's primary pattern is empty and matches every line, --files or not
+    files = bool(files) and bool(pats)
+    torch.cuda.synchronize()
+    sel, nlines, _ = select_lines_bool(dev.data_ptr(), n, lists, clauses, invert, files)
+    rec = torch.zeros((3, max(sel, 1)), dtype=torch.int64, device=dev.device)
+    torch.cuda.synchronize()
+    select_lines_bool(dev.data_ptr(), n, lists, clauses, invert, files, rec[0].data_ptr(), rec[1].data_ptr(),
+                      rec[2].data_ptr(), sel)
+    out = _with_context(dev, n, rec, sel, nlines, before, after)
+    del keep, found
+    return out
 
 
 def check_utf8(dptr, length, stream=0):
