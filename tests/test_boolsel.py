@@ -326,6 +326,63 @@ def test_many_waves(U):
     _check(U, d, lists, [(1, 2), (4, 0), (3, 8)], "64 MiB", flags=[(False, False)])
 
 
+# ---------------------------------------------------------------- the workspace the line calls share
+def test_shared_workspace_changing_slots(U):
+    """The one-list call, the 16-list call and line_spans take their per-wave
+    arrays from one pooled workspace: 4, 19 and 1 arrays per wave, over 4, 257
+    and 1 wave ranges in turn (it grows, then is reused smaller); lines runs
+    between them from its own."""
+    import torch
+    rng = np.random.default_rng(23)
+    for n in (3 * 4096 + 5, (1 << 20) + 7, 100):
+        d = np.where(rng.random(n) < 0.04, 10, 101).astype(np.uint8)
+        buf = _dev(d)
+        lists = []
+        for t in range(16):
+            st = np.sort(rng.choice(n, size=min(n, int(rng.integers(1, 200))), replace=False))
+            lists.append((st, rng.integers(0, 60, len(st)).astype(np.uint32)))
+        dl, keep = _dev_lists(lists)
+        # select_lines with one list
+        starts, lens = lists[0]
+        wb, we, wl, wn = M.select(d, starts, lens, False)
+        torch.cuda.synchronize()
+        sel, lines = U.select_lines(buf.data_ptr(), n, dl[0][0], dl[0][1], dl[0][2], False)
+        rec = torch.full((3, sel + 3), CANARY, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        assert U.select_lines(buf.data_ptr(), n, dl[0][0], dl[0][1], dl[0][2], False, rec[0].data_ptr(),
+                              rec[1].data_ptr(), rec[2].data_ptr(), sel) == (sel, lines)
+        torch.cuda.synchronize()
+        r = _u64(rec)
+        assert (sel, lines) == (len(wl), wn), n
+        assert (r[:, sel:] == CANARY).all()
+        assert np.array_equal(r[0, :sel], wb) and np.array_equal(r[1, :sel], we) and np.array_equal(r[2, :sel], wl), n
+        # select_lines_bool over 16 lists, one clause naming all of them
+        _check(U, d, lists, [(0x5555, 0xaaaa), (1, 0)], "shared workspace, %d bytes" % n, flags=[(False, False)],
+               buf=buf)
+        # line_spans for every line
+        nlines = M.line_table(d)[0].size
+        q = np.arange(1, nlines + 1, dtype=np.uint64)
+        qd = torch.from_numpy(q.view(np.int64).copy()).to("cuda")
+        out = torch.full((2, len(q) + 2), CANARY, dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        U.line_spans(buf.data_ptr(), n, qd.data_ptr(), len(q), out[0].data_ptr(), out[1].data_ptr())
+        torch.cuda.synchronize()
+        r = _u64(out)
+        sb, se = M.spans(d, q)
+        assert (r[:, len(q):] == CANARY).all()
+        assert np.array_equal(r[0, :len(q)], sb) and np.array_equal(r[1, :len(q)], se), n
+        # lines
+        ln = torch.zeros(len(starts), dtype=torch.int64, device="cuda")
+        torch.cuda.synchronize()
+        nl, ml = U.lines(buf.data_ptr(), n, dl[0][0], len(starts), ln.data_ptr())
+        torch.cuda.synchronize()
+        nlpos = np.flatnonzero(d == 10)
+        want = 1 + np.searchsorted(nlpos, np.asarray(starts, dtype=np.int64), side="left")
+        assert (nl, ml) == (len(nlpos), len(np.unique(want))), n
+        assert np.array_equal(ln.cpu().numpy(), want), n
+        del keep
+
+
 # ---------------------------------------------------------------- capacity and arguments
 def test_capacity_and_invalid_arguments(U):
     import torch

@@ -1,0 +1,239 @@
+// line_host.hpp -- the host layer of the line calls (lines.hip, linesel.hip,
+// linebool.hip): error reporting, the wave ranges, the per-device workspace
+// pool, the newline count with its prefix, and the driver of the two selection
+// calls.
+#pragma once
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/ugpu.h"
+#include "plan.hpp"
+#include "scan_kernels.hpp"
+
+namespace ugpu {
+
+inline int fail(int code, const std::string& msg) { return host_fail(code, msg); }
+
+inline int hip_fail(hipError_t e, const char* what)
+{
+  return host_fail(UGPU_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The wave ranges of the line kernels for a buffer of len bytes: whole tiles,
+// about 16 waves per CU, at most kMaxRec.  Returns the current device, or -1
+// with the error recorded.
+inline int line_wave_ranges(uint64_t len, uint64_t* per, uint64_t* nwaves)
+{
+  int dev = 0, cus = 256;
+  hipError_t e;
+  if ((e = hipGetDevice(&dev)) != hipSuccess ||
+      (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) {
+    hip_fail(e, "device query");
+    return -1;
+  }
+  const uint64_t tile = lines_tile();
+  const uint64_t tiles = (len + tile - 1) / tile;
+  uint64_t want = (uint64_t)cus * 16;
+  if (want > (uint64_t)kMaxRec) want = kMaxRec;
+  uint64_t tpw = tiles ? (tiles + want - 1) / want : 1;
+  while (tpw * tile > kMaxRecBytes) --tpw;  // (never for sane sizes; 32-bit offsets)
+  if (tpw == 0) tpw = 1;
+  *per = tpw * tile;
+  *nwaves = tiles ? (tiles + tpw - 1) / tpw : 1;
+  return dev;
+}
+
+// A workspace of type W (with an int dev) taken from the idle ones of its
+// device for the length of a call, so that repeated calls do no hipMalloc or
+// hipFree (hipFree synchronises the device).  Idle workspaces are kept for the
+// process lifetime.  ws is NULL when none could be made.
+template <class W>
+struct WsLease {
+  W* ws = nullptr;
+
+  explicit WsLease(int dev)
+  {
+    Pool& p = pool();
+    std::lock_guard<std::mutex> lk(p.mu);
+    for (size_t i = 0; i < p.idle.size(); ++i)
+      if (p.idle[i]->dev == dev) {
+        ws = p.idle[i];
+        p.idle.erase(p.idle.begin() + (long)i);
+        return;
+      }
+    ws = new (std::nothrow) W;
+    if (ws) ws->dev = dev;
+  }
+  ~WsLease()
+  {
+    if (!ws) return;
+    Pool& p = pool();
+    std::lock_guard<std::mutex> lk(p.mu);
+    p.idle.push_back(ws);
+  }
+  WsLease(const WsLease&) = delete;
+  WsLease& operator=(const WsLease&) = delete;
+  W* operator->() const { return ws; }
+
+ private:
+  struct Pool {
+    std::mutex mu;
+    std::vector<W*> idle;
+  };
+  static Pool& pool()
+  {
+    static Pool p;
+    return p;
+  }
+};
+
+// `slots` per-wave uint64_t arrays the kernels write (d_out: array s is
+// d_out + s * nw), as many the host stitches for them (d_in), and pinned host
+// copies of both.  Grows only.
+struct WaveWs {
+  int dev = -1;
+  uint64_t cap = 0;  // values each way
+  uint64_t* d_out = nullptr;
+  uint64_t* d_in = nullptr;
+  uint64_t* h_out = nullptr;
+  uint64_t* h_in = nullptr;
+
+  void release()
+  {
+    (void)hipFree(d_out);
+    (void)hipFree(d_in);
+    (void)hipHostFree(h_out);
+    (void)hipHostFree(h_in);
+    d_out = d_in = h_out = h_in = nullptr;
+    cap = 0;
+  }
+
+  hipError_t reserve(uint64_t nw, uint64_t slots)
+  {
+    hipError_t e = hipSuccess;
+    if (nw * slots > cap) {
+      release();
+      const size_t bytes = nw * slots * 8;
+      if ((e = hipMalloc(&d_out, bytes)) != hipSuccess || (e = hipMalloc(&d_in, bytes)) != hipSuccess ||
+          (e = hipHostMalloc(&h_out, bytes)) != hipSuccess || (e = hipHostMalloc(&h_in, bytes)) != hipSuccess) {
+        release();
+        return e;
+      }
+      cap = nw * slots;
+    }
+    return e;
+  }
+};
+
+// nl_count_kernel over L's wave ranges into array 0 of ws.d_out, then `also`
+// (further launches writing arrays 1 .. back-1); the `back` arrays are copied to
+// ws.h_out and the stream is synchronised.  Leaves the exclusive prefix of the
+// newline counts in array 0 of ws.h_in and their sum in *newlines.
+template <class Also>
+hipError_t newline_prefix(WaveWs& ws, LinesParams L, bool sparse, uint64_t back, Also also, hipStream_t st,
+                          uint64_t* newlines)
+{
+  L.counts = ws.d_out;
+  hipError_t e;
+  if ((e = launch_nl_count(L, sparse, st)) != hipSuccess || (e = also()) != hipSuccess ||
+      (e = hipMemcpyAsync(ws.h_out, ws.d_out, L.nwaves * back * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipStreamSynchronize(st)) != hipSuccess)
+    return e;
+  uint64_t total = 0;
+  for (uint64_t i = 0; i < L.nwaves; ++i) {
+    ws.h_in[i] = total;
+    total += ws.h_out[i];
+  }
+  *newlines = total;
+  return hipSuccess;
+}
+
+inline hipError_t newline_prefix(WaveWs& ws, const LinesParams& L, bool sparse, hipStream_t st, uint64_t* newlines)
+{
+  return newline_prefix(ws, L, sparse, 1, [] { return hipSuccess; }, st, newlines);
+}
+
+inline LinesParams line_ranges_params(const uint8_t* g, uint64_t len, uint64_t per, uint64_t nw)
+{
+  LinesParams L{};
+  L.g = g;
+  L.len = len;
+  L.per = per;
+  L.nwaves = nw;
+  return L;
+}
+
+// The selection call over ncover match lists (ugpu_select_lines: 1;
+// ugpu_select_lines_bool: the lists its formula uses).  c holds the buffer,
+// invert and the record arrays; the driver sets the wave ranges and the
+// per-wave arrays, laid out as: newline counts / prefix, last newline / line
+// begin, ncover covers, selected counts / output offsets.  Three host round
+// trips, two when it only counts:
+//   newline count and summary(); the stitch: prefix sum of the counts, prefix
+//   maxima of the others; decide(final covers) may then change the pass's
+//   parameters and returns the whole-input truth, or -1 for "some line is
+//   selected";
+//   pass(false), the count pass; the exclusive prefix of its counts; *selected,
+//   *whole and the capacity check;
+//   pass(true), the write pass.
+template <class P, class Summary, class Decide, class Pass>
+int select_lines_driver(P& c, uint32_t ncover, uint64_t capacity, uint64_t* selected, uint64_t* lines,
+                        int* whole, hipStream_t st, Summary summary, Decide decide, Pass pass)
+{
+  const bool want = c.begin || c.end || c.lineno;
+  if (want && !(c.begin && c.end && c.lineno)) return fail(UGPU_INVAL, "give all three record arrays or none");
+  const int dev = line_wave_ranges(c.len, &c.per, &c.nwaves);
+  if (dev < 0) return UGPU_DEVICE;
+  WsLease<WaveWs> ws(dev);
+  if (!ws.ws) return fail(UGPU_NOMEM, "line selection workspace");
+  const uint64_t nw = c.nwaves, nsum = 2 + ncover, last = nsum * nw;  // last: the selected counts
+  hipError_t e = ws->reserve(nw, nsum + 1);
+  if (e != hipSuccess) return hip_fail(e, "line selection buffers");
+  c.lastnl = ws->d_out + nw;
+  c.mcover = ws->d_out + 2 * nw;
+  c.selcnt = ws->d_out + last;
+  c.prefix = ws->d_in;
+  c.bol = ws->d_in + nw;
+  c.cover = ws->d_in + 2 * nw;
+  c.obase = ws->d_in + last;
+  uint64_t total = 0;
+  if ((e = newline_prefix(*ws.ws, line_ranges_params(c.g, c.len, c.per, nw), false, nsum, summary, st, &total)) !=
+      hipSuccess)
+    return hip_fail(e, "line summary");
+  // stitch: begin of the open line and each list's match cover before each range
+  uint64_t bol = 0, cover[kBoolLists] = {};
+  for (uint64_t i = 0; i < nw; ++i) {
+    ws->h_in[nw + i] = bol;
+    if (ws->h_out[nw + i]) bol = ws->h_out[nw + i];
+    for (uint32_t t = 0; t < ncover; ++t) {
+      const uint64_t at = (2 + (uint64_t)t) * nw + i;
+      ws->h_in[at] = cover[t];
+      if (ws->h_out[at] > cover[t]) cover[t] = ws->h_out[at];
+    }
+  }
+  if (lines) *lines = total + (bol < c.len ? 1 : 0);
+  const int truth = decide(cover);
+  if ((e = hipMemcpyAsync(ws->d_in, ws->h_in, nw * nsum * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = pass(false)) != hipSuccess ||
+      (e = hipMemcpyAsync(ws->h_out + last, ws->d_out + last, nw * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipStreamSynchronize(st)) != hipSuccess)
+    return hip_fail(e, "line selection count");
+  uint64_t nsel = 0;
+  for (uint64_t i = 0; i < nw; ++i) {
+    ws->h_in[last + i] = nsel;
+    nsel += ws->h_out[last + i];
+  }
+  if (selected) *selected = nsel;
+  if (whole) *whole = truth >= 0 ? truth : (nsel ? 1 : 0);
+  if (want && nsel > capacity) return fail(UGPU_CAPACITY, "line record arrays too small");
+  if (want && nsel) {
+    if ((e = hipMemcpyAsync(ws->d_in + last, ws->h_in + last, nw * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = pass(true)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+      return hip_fail(e, "line selection write");
+  }
+  return UGPU_OK;
+}
+
+}  // namespace ugpu

@@ -1,4 +1,4 @@
-// line_tiles.hpp -- device helpers of the line-record kernels (linesel.hip,
+// line_tiles.hpp -- device helpers of the line kernels (lines.hip, linesel.hip,
 // linebool.hip): the 4 KiB tile loads, the 16-byte granule newline masks with
 // their prefix, rank_of / mark / select_nl on them, the wave scans and the
 // 64-ary search of a sorted match list.  Everything is per wave.
@@ -85,8 +85,9 @@ struct SRange {
   uint64_t lo, hi;  // byte range [lo, hi) of this wave
   uint32_t n;       // tiles
   uint32_t rel;     // bytes of the range (hi - lo)
-  uint32_t rel16;   // rel rounded up to 16: the loads' bound (a ragged end is
-                    // loaded whole, inside the aligned 16-byte granule, and
+  uint32_t rel16;   // rel rounded up to 16: the loads' bound (a buffer load
+                    // past num_records zeroes the whole dword, so a ragged end
+                    // is loaded whole, inside the aligned 16-byte granule, and
                     // masked with granule_valid)
 };
 

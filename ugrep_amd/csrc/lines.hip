@@ -25,104 +25,14 @@
 //                    with ds_bpermute, so the second pass reads ~1 KiB per
 //                    match instead of the whole buffer.
 #include "device_common.hpp"
+#include "line_host.hpp"
+#include "line_tiles.hpp"
 
 namespace ugpu {
 
 namespace {
 
-constexpr int kLTile = 4096;
-constexpr int kLWaves = 4;
-
-__device__ __forceinline__ uint4 lload16(__amdgpu_buffer_rsrc_t rs, uint32_t off)
-{
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-  const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 2 /* nt */);
-  return uint4{v.x, v.y, v.z, v.w};
-}
-
-// bit 7 of each byte set iff the byte is '\n' (exact: no carries between bytes)
-__device__ __forceinline__ uint32_t nl_bits(uint32_t x)
-{
-  const uint32_t t = x ^ 0x0a0a0a0au;
-  const uint32_t nz = ((t & 0x7f7f7f7fu) + 0x7f7f7f7fu) | t;
-  return ~nz & 0x80808080u;
-}
-
-// 4-bit mask of newline bytes of a dword
-__device__ __forceinline__ uint32_t nl4(uint32_t x) { return ((nl_bits(x) >> 7) * 0x01020408u) >> 24; }
-
-__device__ __forceinline__ uint32_t nl16(const uint4& v)
-{
-  return nl4(v.x) | (nl4(v.y) << 4) | (nl4(v.z) << 8) | (nl4(v.w) << 12);
-}
-
-// Tile i of the range starting at wbase (rel = readable bytes from wbase).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ltile(const uint8_t* wbase, uint32_t i, uint32_t rel)
-{
-  const uint32_t off = i * (uint32_t)kLTile;
-  const uint32_t n = rel > off ? rel - off : 0u;
-  const int nr = __builtin_amdgcn_readfirstlane((int)(n < (uint32_t)kLTile ? n : (uint32_t)kLTile));
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(wbase + off), (short)0, nr, 0x00020000);
-}
-
-__device__ __forceinline__ uint32_t lscan_add(uint32_t v)
-{
-  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-  return v;
-}
-
-struct LRange {
-  uint64_t lo, hi;  // byte range [lo, hi) of this wave
-  uint32_t n;       // tiles
-  uint32_t rel;     // bytes of the range (hi - lo)
-  uint32_t rel16;   // rel rounded up to 16: the loads' bound (a buffer load
-                    // past num_records zeroes the whole dword, so a ragged end
-                    // is loaded whole, inside the aligned 16-byte granule, and
-                    // masked with granule_valid)
-};
-
-// 16-bit mask of the bytes of granule [off, off+16) that lie below rel
-__device__ __forceinline__ uint32_t granule_valid(uint32_t rel, uint32_t off)
-{
-  const uint32_t rem = rel > off ? rel - off : 0u;
-  return rem >= 16u ? 0xffffu : (1u << rem) - 1u;
-}
-
-__device__ __forceinline__ LRange lrange(const LinesParams& L, uint64_t gw)
-{
-  LRange r;
-  r.lo = gw * L.per;
-  if (r.lo > L.len) r.lo = L.len;
-  r.hi = r.lo + L.per < L.len ? r.lo + L.per : L.len;
-  r.n = (uint32_t)((r.hi - r.lo + kLTile - 1) / kLTile);
-  r.rel = (uint32_t)(r.hi - r.lo);
-  r.rel16 = (r.rel + 15u) & ~15u;
-  return r;
-}
-
-// First match with start >= lo: 64-ary search over the sorted starts.
-__device__ __forceinline__ uint64_t first_match(const LinesParams& L, uint64_t lo, int lane)
-{
-  uint64_t a = 0, b = L.nmatch;  // answer in [a, b]
-  while (b - a > 64) {
-    const uint64_t step = (b - a + 63) / 64;
-    const uint64_t idx = a + step * (uint64_t)lane;
-    const bool below = idx < b && L.starts[idx] < lo;
-    const int cntb = __popcll(__ballot(below));  // pivots below lo (a prefix of the lanes)
-    const uint64_t na = cntb ? a + step * (uint64_t)(cntb - 1) + 1 : a;
-    const uint64_t nb = a + step * (uint64_t)cntb;
-    a = na;
-    b = nb < b ? nb : b;
-  }
-  const uint64_t idx = a + (uint64_t)lane;
-  const bool below = idx < b && L.starts[idx] < lo;
-  return a + __popcll(__ballot(below));
-}
+// (tile loads, newline masks, scans, srange, lower64, tile_masks: line_tiles.hpp)
 
 // Per-wave -c bookkeeping over the wave's matches in order, 64 at a time
 // (lanes holding a match form a prefix).
@@ -157,27 +67,27 @@ struct LineStats {
 }  // namespace
 
 template <bool SPARSE>
-__global__ __launch_bounds__(kLWaves * 64) void nl_count_kernel(LinesParams L)
+__global__ __launch_bounds__(kSWaves * 64) void nl_count_kernel(LinesParams L)
 {
   const int lane = threadIdx.x & 63;
-  const uint64_t gw = (uint64_t)blockIdx.x * kLWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t gw = (uint64_t)blockIdx.x * kSWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (gw >= L.nwaves) return;
-  const LRange r = lrange(L, gw);
+  const SRange r = srange(L.len, L.per, gw);
   uint32_t cnt = 0;
   for (uint32_t i = 0; i < r.n; ++i) {
     const __amdgpu_buffer_rsrc_t rs = ltile(L.g + r.lo, i, r.rel16);
     uint32_t c[4];
-    if ((i + 1u) * (uint32_t)kLTile <= r.rel) {  // whole tile (uniform branch)
+    if ((i + 1u) * (uint32_t)kSTile <= r.rel) {  // whole tile (uniform branch)
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const uint4 v = lload16(rs, 16u * lane + 1024u * k);
+        const uint4 v = sload16(rs, 16u * lane + 1024u * k);
         c[k] = __popc(nl_bits(v.x)) + __popc(nl_bits(v.y)) + __popc(nl_bits(v.z)) + __popc(nl_bits(v.w));
       }
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const uint32_t o = 16u * lane + 1024u * k;
-        c[k] = __popc(nl16(lload16(rs, o)) & granule_valid(r.rel, i * (uint32_t)kLTile + o));
+        c[k] = __popc(nl16(sload16(rs, o)) & granule_valid(r.rel, i * (uint32_t)kSTile + o));
       }
     }
     cnt += c[0] + c[1] + c[2] + c[3];
@@ -185,52 +95,33 @@ __global__ __launch_bounds__(kLWaves * 64) void nl_count_kernel(LinesParams L)
       const uint32_t p01 = (uint32_t)__builtin_amdgcn_readlane(lscan_add(c[0] | (c[1] << 16)), 63);
       const uint32_t p23 = (uint32_t)__builtin_amdgcn_readlane(lscan_add(c[2] | (c[3] << 16)), 63);
       if (lane == 0)
-        reinterpret_cast<uint64_t*>(L.qcount)[(r.lo / kLTile) + i] = (uint64_t)p01 | ((uint64_t)p23 << 32);
+        reinterpret_cast<uint64_t*>(L.qcount)[(r.lo / kSTile) + i] = (uint64_t)p01 | ((uint64_t)p23 << 32);
     }
   }
   const uint64_t t = wave_sum(cnt);
   if (lane == 0) L.counts[gw] = t;
 }
 
-__global__ __launch_bounds__(kLWaves * 64) void nl_assign_kernel(LinesParams L)
+__global__ __launch_bounds__(kSWaves * 64) void nl_assign_kernel(LinesParams L)
 {
-  __shared__ uint16_t gmask[kLWaves][256], gpre[kLWaves][256];
+  __shared__ uint16_t gmask[kSWaves][256], gpre[kSWaves][256];
   const int lane = threadIdx.x & 63;
   const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const uint64_t gw = (uint64_t)blockIdx.x * kLWaves + wid;
+  const uint64_t gw = (uint64_t)blockIdx.x * kSWaves + wid;
   if (gw >= L.nwaves) return;
-  const LRange r = lrange(L, gw);
-  uint64_t j = first_match(L, r.lo, lane);  // next match to assign
+  const SRange r = srange(L.len, L.per, gw);
+  uint64_t j = lower64(L.starts, L.nmatch, r.lo, lane);  // next match to assign
   uint64_t line = 1 + L.prefix[gw];         // line of byte r.lo
   LineStats st;
   uint16_t* gm = gmask[wid];
   uint16_t* gp = gpre[wid];
   for (uint32_t i = 0; i < r.n && j < L.nmatch; ++i) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the previous tile's LDS reads precede these writes
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint64_t ts = r.lo + (uint64_t)i * kLTile;
-    const __amdgpu_buffer_rsrc_t rs = ltile(L.g + r.lo, i, r.rel16);
+    wave_sync();  // the previous tile's LDS reads precede these writes
+    const uint64_t ts = r.lo + (uint64_t)i * kSTile;
     uint32_t c[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t o = 16u * lane + 1024u * k;
-      const uint32_t m = nl16(lload16(rs, o)) & granule_valid(r.rel, i * (uint32_t)kLTile + o);
-      gm[64 * k + lane] = (uint16_t)m;
-      c[k] = __popc(m);
-    }
-    // exclusive prefix over granules g = 64 k + lane (tile order)
-    uint32_t base = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t incl = lscan_add(c[k]);
-      gp[64 * k + lane] = (uint16_t)(base + incl - c[k]);
-      base += (uint32_t)__builtin_amdgcn_readlane(incl, 63);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const uint64_t tend = ts + kLTile < r.hi ? ts + kLTile : r.hi;
+    const uint32_t base = tile_masks(L.g, r, i, lane, gm, gp, c);
+    wave_sync();
+    const uint64_t tend = ts + kSTile < r.hi ? ts + kSTile : r.hi;
     for (;;) {  // matches starting in this tile, 64 at a time
       const uint64_t idx = j + (uint64_t)lane;
       const uint64_t s = idx < L.nmatch ? L.starts[idx] : ~0ull;
@@ -239,8 +130,7 @@ __global__ __launch_bounds__(kLWaves * 64) void nl_assign_kernel(LinesParams L)
       if (!mb) break;
       uint64_t ln = 0;
       if (in) {
-        const uint32_t o = (uint32_t)(s - ts), g = o >> 4;
-        ln = line + gp[g] + __popc((uint32_t)gm[g] & ((1u << (o & 15)) - 1u));
+        ln = line + rank_of(gm, gp, (uint32_t)(s - ts));
         if (L.lines) L.lines[idx] = ln;
       }
       st.add(ln, in, mb, lane);
@@ -254,13 +144,13 @@ __global__ __launch_bounds__(kLWaves * 64) void nl_assign_kernel(LinesParams L)
   st.store(L.recs + gw, lane);
 }
 
-__global__ __launch_bounds__(kLWaves * 64) void nl_assign_sparse_kernel(LinesParams L)
+__global__ __launch_bounds__(kSWaves * 64) void nl_assign_sparse_kernel(LinesParams L)
 {
   const int lane = threadIdx.x & 63;
-  const uint64_t gw = (uint64_t)blockIdx.x * kLWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint64_t gw = (uint64_t)blockIdx.x * kSWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (gw >= L.nwaves) return;
-  const LRange r = lrange(L, gw);
-  uint64_t j = first_match(L, r.lo, lane);
+  const SRange r = srange(L.len, L.per, gw);
+  uint64_t j = lower64(L.starts, L.nmatch, r.lo, lane);
   uint64_t line = 1 + L.prefix[gw];
   LineStats st;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
@@ -285,7 +175,7 @@ __global__ __launch_bounds__(kLWaves * 64) void nl_assign_sparse_kernel(LinesPar
       const uint64_t qe = qs + kLinesQuarter < r.hi ? qs + kLinesQuarter : r.hi;
       const uint64_t qline = line + (uint32_t)__builtin_amdgcn_readlane(excl, (int)(q - qb));
       const uint32_t go = qo + 16u * lane;
-      const uint32_t m = nl16(lload16(rs, go)) & granule_valid(r.rel, go);
+      const uint32_t m = nl16(sload16(rs, go)) & granule_valid(r.rel, go);
       const uint32_t cm = __popc(m);
       const uint32_t pre = lscan_add(cm) - cm;
       for (;;) {  // matches in this quarter, 64 at a time
@@ -314,24 +204,119 @@ __global__ __launch_bounds__(kLWaves * 64) void nl_assign_sparse_kernel(LinesPar
 
 hipError_t launch_nl_count(const LinesParams& L, bool sparse, hipStream_t stream)
 {
-  const uint32_t grid = (uint32_t)((L.nwaves + kLWaves - 1) / kLWaves);
+  const uint32_t grid = (uint32_t)((L.nwaves + kSWaves - 1) / kSWaves);
   if (sparse)
-    hipLaunchKernelGGL(nl_count_kernel<true>, dim3(grid), dim3(kLWaves * 64), 0, stream, L);
+    hipLaunchKernelGGL(nl_count_kernel<true>, dim3(grid), dim3(kSWaves * 64), 0, stream, L);
   else
-    hipLaunchKernelGGL(nl_count_kernel<false>, dim3(grid), dim3(kLWaves * 64), 0, stream, L);
+    hipLaunchKernelGGL(nl_count_kernel<false>, dim3(grid), dim3(kSWaves * 64), 0, stream, L);
   return hipGetLastError();
 }
 
 hipError_t launch_nl_assign(const LinesParams& L, bool sparse, hipStream_t stream)
 {
-  const uint32_t grid = (uint32_t)((L.nwaves + kLWaves - 1) / kLWaves);
+  const uint32_t grid = (uint32_t)((L.nwaves + kSWaves - 1) / kSWaves);
   if (sparse)
-    hipLaunchKernelGGL(nl_assign_sparse_kernel, dim3(grid), dim3(kLWaves * 64), 0, stream, L);
+    hipLaunchKernelGGL(nl_assign_sparse_kernel, dim3(grid), dim3(kSWaves * 64), 0, stream, L);
   else
-    hipLaunchKernelGGL(nl_assign_kernel, dim3(grid), dim3(kLWaves * 64), 0, stream, L);
+    hipLaunchKernelGGL(nl_assign_kernel, dim3(grid), dim3(kSWaves * 64), 0, stream, L);
   return hipGetLastError();
 }
 
-uint32_t lines_tile() { return kLTile; }
+uint32_t lines_tile() { return kSTile; }
 
 }  // namespace ugpu
+
+// ---------------------------------------------------------------- C ABI
+using namespace ugpu;
+
+namespace {
+
+// Per-call scratch of ugpu_lines beside the per-wave counts and prefixes:
+// per-wave -c records with their pinned host copy, and quarter counts (sparse
+// mode).
+struct LinesWs : WaveWs {
+  uint64_t rec_cap = 0, q_cap = 0;
+  LineRec* d_rec = nullptr;
+  LineRec* h_rec = nullptr;
+  uint16_t* d_qc = nullptr;
+
+  hipError_t reserve(uint64_t nw, uint64_t quarters)
+  {
+    hipError_t e = WaveWs::reserve(nw, 1);
+    if (e != hipSuccess) return e;
+    if (nw > rec_cap) {
+      (void)hipFree(d_rec);
+      (void)hipHostFree(h_rec);
+      d_rec = h_rec = nullptr;
+      rec_cap = 0;
+      if ((e = hipMalloc(&d_rec, nw * sizeof(LineRec))) != hipSuccess ||
+          (e = hipHostMalloc(&h_rec, nw * sizeof(LineRec))) != hipSuccess)
+        return e;
+      rec_cap = nw;
+    }
+    if (quarters > q_cap) {
+      (void)hipFree(d_qc);
+      d_qc = nullptr;
+      q_cap = 0;
+      if ((e = hipMalloc(&d_qc, quarters * 2)) != hipSuccess) return e;
+      q_cap = quarters;
+    }
+    return e;
+  }
+};
+
+}  // namespace
+
+int ugpu_lines(const uint8_t* dbuf, uint64_t len, const uint64_t* d_start, uint64_t n, uint64_t* d_line,
+               uint64_t* newlines, uint64_t* matching_lines, void* stream)
+{
+  if (!dbuf || (n && !d_start)) return fail(UGPU_INVAL, "NULL argument");
+  if (reinterpret_cast<uintptr_t>(dbuf) & 15u) return fail(UGPU_INVAL, "buffer must be 16-byte aligned");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  uint64_t per = 0, nw = 0;
+  const int dev = line_wave_ranges(len, &per, &nw);
+  if (dev < 0) return UGPU_DEVICE;
+  // sparse assign pass when matches are rarer than one per two quarters
+  // (UGPU_LINES_MODE=1/2 forces dense/sparse, for tests)
+  const uint64_t quarters = (len + kSTile - 1) / kSTile * (kSTile / kLinesQuarter);
+  bool sparse = n > 0 && n * 2 < quarters;
+  if (const char* mo = getenv("UGPU_LINES_MODE")) {
+    if (mo[0] == '1') sparse = false;
+    if (mo[0] == '2') sparse = n > 0;
+  }
+  WsLease<LinesWs> ws(dev);
+  if (!ws.ws) return fail(UGPU_NOMEM, "lines workspace");
+  hipError_t e = ws->reserve(nw, sparse ? quarters : 0);
+  if (e != hipSuccess) return hip_fail(e, "lines buffers");
+  LinesParams L = line_ranges_params(dbuf, len, per, nw);
+  L.starts = d_start;
+  L.nmatch = n;
+  L.lines = d_line;
+  L.counts = ws->d_out;
+  L.prefix = ws->d_in;
+  L.recs = ws->d_rec;
+  L.qcount = sparse ? ws->d_qc : nullptr;
+  uint64_t total = 0;
+  if ((e = newline_prefix(*ws.ws, L, sparse, st, &total)) != hipSuccess) return hip_fail(e, "newline count");
+  if (newlines) *newlines = total;
+  if (n > 0 || matching_lines) {
+    if ((e = hipMemcpyAsync(ws->d_in, ws->h_in, nw * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+        (e = launch_nl_assign(L, sparse, st)) != hipSuccess ||
+        (e = hipMemcpyAsync(ws->h_rec, ws->d_rec, nw * sizeof(LineRec), hipMemcpyDeviceToHost, st)) != hipSuccess ||
+        (e = hipStreamSynchronize(st)) != hipSuccess)
+      return hip_fail(e, "line assignment");
+    // lines of consecutive matches in different waves may coincide
+    uint64_t lines = 0, last = 0;
+    bool any = false;
+    for (uint64_t i = 0; i < nw; ++i) {
+      const LineRec& r = ws->h_rec[i];
+      if (!r.nmatch) continue;
+      lines += r.trans;
+      if (any && r.first_line == last) --lines;
+      last = r.last_line;
+      any = true;
+    }
+    if (matching_lines) *matching_lines = lines;
+  }
+  return UGPU_OK;
+}

@@ -29,32 +29,14 @@
 // matches starting in the tile, 64 per step, set the bits of the lines they
 // touch; `cover` (exclusive end of the bytes touched by earlier matches)
 // carries a match across tiles and ranges.
-#include <mutex>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/ugpu.h"
 #include "device_common.hpp"
-#include "line_tiles.hpp"
-#include "plan.hpp"
+#include "line_host.hpp"
+#include "line_select.hpp"
 
 namespace ugpu {
 
-namespace {
-
-// (tile loads, newline masks, rank_of / mark, scans, lower64: line_tiles.hpp)
-
-// Exclusive end of the bytes match idx (start s < len) touches: a zero-length
-// match touches byte s.
-__device__ __forceinline__ uint64_t match_end(const SelParams& S, uint64_t idx, uint64_t s)
-{
-  const uint64_t l = S.lens ? (uint64_t)S.lens[idx] : 0ull;
-  const uint64_t e = l ? s + l : s + 1;
-  return e < S.len ? e : S.len;
-}
-
-}  // namespace
+// (tiles, masks, rank_of / mark, scans, lower64: line_tiles.hpp; the steps of
+// the walk shared with bool_kernel: line_select.hpp)
 
 __global__ __launch_bounds__(kSWaves * 64) void sel_summary_kernel(SelParams S)
 {
@@ -62,29 +44,8 @@ __global__ __launch_bounds__(kSWaves * 64) void sel_summary_kernel(SelParams S)
   const uint64_t gw = (uint64_t)blockIdx.x * kSWaves + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (gw >= S.nwaves) return;
   const SRange r = srange(S.len, S.per, gw);
-  uint64_t last = 0;  // 1 + position of the range's last newline
-  for (uint32_t i = r.n; i-- > 0;) {
-    const __amdgpu_buffer_rsrc_t rs = ltile(S.g + r.lo, i, r.rel16);
-    uint32_t best = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t o = 16u * lane + 1024u * k;
-      const uint32_t m = nl16(sload16(rs, o)) & granule_valid(r.rel, i * (uint32_t)kSTile + o);
-      if (m) best = umax(best, o + 32u - (uint32_t)__builtin_clz(m));
-    }
-    best = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_max(best));
-    if (best) {
-      last = r.lo + (uint64_t)i * kSTile + best;
-      break;
-    }
-  }
-  const uint64_t j0 = lower64(S.starts, S.nmatch, r.lo, lane), j1 = lower64(S.starts, S.nmatch, r.hi, lane);
-  uint64_t cv = 0;
-  for (uint64_t idx = j0 + (uint64_t)lane; idx < j1; idx += 64) {
-    const uint64_t e = match_end(S, idx, S.starts[idx]);
-    cv = e > cv ? e : cv;
-  }
-  cv = wave_max(cv);
+  const uint64_t last = last_newline(S.g, r, lane);
+  const uint64_t cv = range_cover(S.starts, S.lens, S.nmatch, S.len, r, lane);
   if (lane == 0) {
     S.lastnl[gw] = last;
     S.mcover[gw] = cv;
@@ -119,50 +80,24 @@ __global__ __launch_bounds__(kSWaves * 64) void sel_kernel(SelParams S)
     for (int w = lane; w < kTbWords; w += 64) tb[w] = 0;
     const uint32_t base = tile_masks(S.g, r, i, lane, gm, gp, c);
     wave_sync();
-    // the open line and the lines after it that earlier matches reach
-    if (cover > bol && lane == 0) {
-      uint32_t hr = 0;
-      if (cover > ts) hr = rank_of(gm, gp, (uint32_t)((cover < tend ? cover : tend) - 1 - ts));
-      mark(tb, 0, hr);
-    }
+    mark_cover(tb, gm, gp, cover, bol, ts, tend, lane);
     if (j < S.nmatch) {
-      uint64_t cl = 0;  // this lane's share of the tile's cover
-      bool hit = false;
-      for (;;) {        // matches starting in this tile, 64 at a time
-        const uint64_t idx = j + (uint64_t)lane;
-        const uint64_t s = idx < S.nmatch ? S.starts[idx] : ~0ull;
-        const bool in = s < tend;
-        const uint64_t mb = __ballot(in);
-        if (!mb) break;
-        hit = true;
-        uint32_t r0 = 0, r1 = 0;
-        if (in) {
-          const uint64_t e = match_end(S, idx, s);
-          cl = e > cl ? e : cl;
-          r0 = rank_of(gm, gp, (uint32_t)(s - ts));
-          r1 = rank_of(gm, gp, (uint32_t)((e < tend ? e : tend) - 1 - ts));
-        }
-        // (matches crowd on a line: one whose only line the lane below has just reached leaves the bit to it)
-        const uint32_t pr1 = (uint32_t)__shfl_up((int)r1, 1, 64);
-        if (in && !(lane && r0 == r1 && pr1 == r0)) mark(tb, r0, r1);
-        const uint32_t k = (uint32_t)__popcll(mb);
-        j += k;
-        if (k < 64) break;
-      }
-      if (hit) {
+      uint64_t cl;
+      const uint64_t j1 = place_matches(tb, gm, gp, S.starts, S.lens, S.nmatch, S.len, j, ts, tend, lane, cl);
+      if (j1 != j) {
         cl = wave_max(cl);
         cover = cl > cover ? cl : cover;
+        j = j1;
       }
     }
     wave_sync();
-    // the lines ending in this tile: granule g's are ranks gp[g] .. gp[g] + c - 1
+    // the lines ending in this tile, per granule: their bits and 1 + tile offset of its last newline
     uint32_t field[4], lp[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint32_t g = 64u * k + lane, r0 = gp[g], m = gm[g];
-      const uint64_t two = (uint64_t)tb[r0 >> 5] | ((uint64_t)tb[(r0 >> 5) + 1] << 32);
-      field[k] = ((uint32_t)(two >> (r0 & 31u)) ^ inv) & ((1u << c[k]) - 1u);
-      lp[k] = m ? 16u * g + 32u - (uint32_t)__builtin_clz(m) : 0u;  // 1 + tile offset of its last newline
+      const uint32_t g = 64u * k + lane;
+      field[k] = granule_field(tb, gp[g], c[k], inv);
+      lp[k] = last_in_granule(gm, g);
     }
     if (WRITE) {
       uint32_t selbase = 0, lastp = 0;
@@ -211,20 +146,8 @@ __global__ __launch_bounds__(kSWaves * 64) void sel_kernel(SelParams S)
     }
   }
   uint64_t total = WRITE ? 0 : wave_sum((uint64_t)nsel);
-  if (gw == S.nwaves - 1 && bol < S.len) {  // the unterminated last line
-    const bool sel = (cover > bol) != (S.invert != 0);
-    if (sel) {
-      if (WRITE) {
-        if (lane == 0) {
-          S.begin[out] = bol;
-          S.end[out] = S.len;
-          S.lineno[out] = line;
-        }
-      } else {
-        ++total;
-      }
-    }
-  }
+  if (gw == S.nwaves - 1 && bol < S.len && (cover > bol) != (S.invert != 0))  // the unterminated last line
+    tail_line<WRITE>(bol, S.len, line, out, lane, S.begin, S.end, S.lineno, total);
   if (!WRITE && lane == 0) S.selcnt[gw] = total;
 }
 
@@ -330,115 +253,6 @@ hipError_t launch_spans(const SpanParams& Q, hipStream_t stream)
 // ---------------------------------------------------------------- C ABI
 using namespace ugpu;
 
-namespace {
-
-int fail(int code, const std::string& msg) { return ugpu::host_fail(code, msg); }
-
-int hip_fail(hipError_t e, const char* what)
-{
-  return ugpu::host_fail(UGPU_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-// Per-call scratch, pooled per device as ugpu_lines' LinesWs (no hipMalloc or
-// hipFree in a repeated call): four per-wave arrays the kernels write (newline
-// counts, last newline, match cover, selected counts), the four the host
-// stitches for them (newline prefix, line begin, cover, output offset) and
-// pinned host copies of both.
-struct SelWs {
-  int dev = -1;
-  uint64_t nw_cap = 0;
-  uint64_t* d_out = nullptr;
-  uint64_t* d_in = nullptr;
-  uint64_t* h_out = nullptr;
-  uint64_t* h_in = nullptr;
-
-  void release()
-  {
-    (void)hipFree(d_out);
-    (void)hipFree(d_in);
-    (void)hipHostFree(h_out);
-    (void)hipHostFree(h_in);
-    d_out = d_in = h_out = h_in = nullptr;
-    nw_cap = 0;
-  }
-
-  hipError_t reserve(uint64_t nw)
-  {
-    hipError_t e = hipSuccess;
-    if (nw > nw_cap) {
-      release();
-      if ((e = hipMalloc(&d_out, nw * 32)) != hipSuccess || (e = hipMalloc(&d_in, nw * 32)) != hipSuccess ||
-          (e = hipHostMalloc(&h_out, nw * 32)) != hipSuccess || (e = hipHostMalloc(&h_in, nw * 32)) != hipSuccess) {
-        release();
-        return e;
-      }
-      nw_cap = nw;
-    }
-    return e;
-  }
-};
-
-std::mutex g_sel_mu;
-std::vector<SelWs*> g_sel_pool;  // idle workspaces (kept for the process lifetime)
-
-SelWs* sel_ws_acquire(int dev)
-{
-  std::lock_guard<std::mutex> lk(g_sel_mu);
-  for (size_t i = 0; i < g_sel_pool.size(); ++i)
-    if (g_sel_pool[i]->dev == dev) {
-      SelWs* w = g_sel_pool[i];
-      g_sel_pool.erase(g_sel_pool.begin() + (long)i);
-      return w;
-    }
-  SelWs* w = new (std::nothrow) SelWs;
-  if (w) w->dev = dev;
-  return w;
-}
-
-void sel_ws_release(SelWs* w)
-{
-  std::lock_guard<std::mutex> lk(g_sel_mu);
-  g_sel_pool.push_back(w);
-}
-
-// wave ranges as ugpu_lines': whole tiles, about 16 waves per CU, at most kMaxRec
-int wave_ranges(uint64_t len, uint64_t* per, uint64_t* nwaves)
-{
-  int dev = 0, cus = 256;
-  hipError_t e;
-  if ((e = hipGetDevice(&dev)) != hipSuccess ||
-      (e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) {
-    hip_fail(e, "device query");
-    return -1;
-  }
-  const uint64_t tile = lines_tile();
-  const uint64_t tiles = (len + tile - 1) / tile;
-  uint64_t want = (uint64_t)cus * 16;
-  if (want > (uint64_t)kMaxRec) want = kMaxRec;
-  uint64_t tpw = tiles ? (tiles + want - 1) / want : 1;
-  while (tpw * tile > kMaxRecBytes) --tpw;
-  if (tpw == 0) tpw = 1;
-  *per = tpw * tile;
-  *nwaves = tiles ? (tiles + tpw - 1) / tpw : 1;
-  return dev;
-}
-
-// nl_count_kernel into ws->d_out[0, nw); leaves the launch on the stream
-hipError_t count_newlines(SelWs* ws, const uint8_t* dbuf, uint64_t len, uint64_t per, uint64_t nw, hipStream_t st)
-{
-  LinesParams L{};
-  L.g = dbuf;
-  L.len = len;
-  L.per = per;
-  L.nwaves = nw;
-  L.counts = ws->d_out;
-  return launch_nl_count(L, false, st);
-}
-
-}  // namespace
-
-int ugpu::line_wave_ranges(uint64_t len, uint64_t* per, uint64_t* nwaves) { return wave_ranges(len, per, nwaves); }
-
 int ugpu_select_lines(const uint8_t* dbuf, uint64_t len, const uint64_t* d_start, const uint32_t* d_len, uint64_t n,
                       uint32_t flags, uint64_t* d_begin, uint64_t* d_end, uint64_t* d_lineno, uint64_t capacity,
                       uint64_t* selected, uint64_t* lines, void* stream)
@@ -446,81 +260,20 @@ int ugpu_select_lines(const uint8_t* dbuf, uint64_t len, const uint64_t* d_start
   if (!dbuf || (n && !d_start)) return fail(UGPU_INVAL, "NULL argument");
   if (reinterpret_cast<uintptr_t>(dbuf) & 15u) return fail(UGPU_INVAL, "buffer must be 16-byte aligned");
   if (flags & ~UGPU_SEL_INVERT) return fail(UGPU_INVAL, "unknown flags");
-  const bool want = d_begin || d_end || d_lineno;
-  if (want && !(d_begin && d_end && d_lineno)) return fail(UGPU_INVAL, "give all three record arrays or none");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  uint64_t per = 0, nw = 0;
-  const int dev = wave_ranges(len, &per, &nw);
-  if (dev < 0) return UGPU_DEVICE;
-  SelWs* ws = sel_ws_acquire(dev);
-  if (!ws) return fail(UGPU_NOMEM, "line selection workspace");
-  hipError_t e = ws->reserve(nw);
-  if (e != hipSuccess) {
-    sel_ws_release(ws);
-    return hip_fail(e, "line selection buffers");
-  }
   SelParams S{};
   S.g = dbuf;
   S.len = len;
-  S.per = per;
-  S.nwaves = nw;
-  S.starts = d_start;
-  S.lens = d_len;
-  S.nmatch = n;
   S.invert = flags & UGPU_SEL_INVERT;
-  S.lastnl = ws->d_out + nw;
-  S.mcover = ws->d_out + 2 * nw;
-  S.selcnt = ws->d_out + 3 * nw;
-  S.prefix = ws->d_in;
-  S.bol = ws->d_in + nw;
-  S.cover = ws->d_in + 2 * nw;
-  S.obase = ws->d_in + 3 * nw;
   S.begin = d_begin;
   S.end = d_end;
   S.lineno = d_lineno;
-  int rc = UGPU_OK;
-  uint64_t nsel = 0;
-  if ((e = count_newlines(ws, dbuf, len, per, nw, st)) != hipSuccess ||
-      (e = launch_sel_summary(S, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(ws->h_out, ws->d_out, nw * 24, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-      (e = hipStreamSynchronize(st)) != hipSuccess) {
-    rc = hip_fail(e, "line summary");
-  } else {
-    // stitch: newlines, begin of the open line and match cover before each range
-    uint64_t total = 0, bol = 0, cover = 0;
-    for (uint64_t i = 0; i < nw; ++i) {
-      ws->h_in[i] = total;
-      ws->h_in[nw + i] = bol;
-      ws->h_in[2 * nw + i] = cover;
-      total += ws->h_out[i];
-      if (ws->h_out[nw + i]) bol = ws->h_out[nw + i];
-      if (ws->h_out[2 * nw + i] > cover) cover = ws->h_out[2 * nw + i];
-    }
-    if (lines) *lines = total + (bol < len ? 1 : 0);
-    if ((e = hipMemcpyAsync(ws->d_in, ws->h_in, nw * 24, hipMemcpyHostToDevice, st)) != hipSuccess ||
-        (e = launch_sel(S, false, st)) != hipSuccess ||
-        (e = hipMemcpyAsync(ws->h_out + 3 * nw, ws->d_out + 3 * nw, nw * 8, hipMemcpyDeviceToHost, st)) !=
-            hipSuccess ||
-        (e = hipStreamSynchronize(st)) != hipSuccess) {
-      rc = hip_fail(e, "line selection count");
-    } else {
-      for (uint64_t i = 0; i < nw; ++i) {
-        ws->h_in[3 * nw + i] = nsel;
-        nsel += ws->h_out[3 * nw + i];
-      }
-      if (selected) *selected = nsel;
-      if (want && nsel > capacity) {
-        rc = fail(UGPU_CAPACITY, "line record arrays too small");
-      } else if (want && nsel) {
-        if ((e = hipMemcpyAsync(ws->d_in + 3 * nw, ws->h_in + 3 * nw, nw * 8, hipMemcpyHostToDevice, st)) !=
-                hipSuccess ||
-            (e = launch_sel(S, true, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
-          rc = hip_fail(e, "line selection write");
-      }
-    }
-  }
-  sel_ws_release(ws);
-  return rc;
+  S.starts = d_start;
+  S.lens = d_len;
+  S.nmatch = n;
+  return select_lines_driver(
+      S, 1, capacity, selected, lines, nullptr, st, [&] { return launch_sel_summary(S, st); },
+      [](const uint64_t*) { return -1; }, [&](bool write) { return launch_sel(S, write, st); });
 }
 
 int ugpu_line_spans(const uint8_t* dbuf, uint64_t len, const uint64_t* d_lineno, uint64_t n, uint64_t* d_begin,
@@ -531,42 +284,27 @@ int ugpu_line_spans(const uint8_t* dbuf, uint64_t len, const uint64_t* d_lineno,
   if (!n) return UGPU_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   uint64_t per = 0, nw = 0;
-  const int dev = wave_ranges(len, &per, &nw);
+  const int dev = line_wave_ranges(len, &per, &nw);
   if (dev < 0) return UGPU_DEVICE;
-  SelWs* ws = sel_ws_acquire(dev);
-  if (!ws) return fail(UGPU_NOMEM, "line span workspace");
-  hipError_t e = ws->reserve(nw);
-  if (e != hipSuccess) {
-    sel_ws_release(ws);
-    return hip_fail(e, "line span buffers");
-  }
-  int rc = UGPU_OK;
-  if ((e = count_newlines(ws, dbuf, len, per, nw, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(ws->h_out, ws->d_out, nw * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-      (e = hipStreamSynchronize(st)) != hipSuccess) {
-    rc = hip_fail(e, "newline count");
-  } else {
-    uint64_t total = 0;
-    for (uint64_t i = 0; i < nw; ++i) {
-      ws->h_in[i] = total;
-      total += ws->h_out[i];
-    }
-    SpanParams Q{};
-    Q.g = dbuf;
-    Q.len = len;
-    Q.per = per;
-    Q.nwaves = nw;
-    Q.q = d_lineno;
-    Q.nq = n;
-    Q.counts = ws->d_out;
-    Q.prefix = ws->d_in;
-    Q.newlines = total;
-    Q.begin = d_begin;
-    Q.end = d_end;
-    if ((e = hipMemcpyAsync(ws->d_in, ws->h_in, nw * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
-        (e = launch_spans(Q, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
-      rc = hip_fail(e, "line spans");
-  }
-  sel_ws_release(ws);
-  return rc;
+  WsLease<WaveWs> ws(dev);
+  if (!ws.ws) return fail(UGPU_NOMEM, "line span workspace");
+  hipError_t e = ws->reserve(nw, 1);
+  if (e != hipSuccess) return hip_fail(e, "line span buffers");
+  SpanParams Q{};
+  if ((e = newline_prefix(*ws.ws, line_ranges_params(dbuf, len, per, nw), false, st, &Q.newlines)) != hipSuccess)
+    return hip_fail(e, "newline count");
+  Q.g = dbuf;
+  Q.len = len;
+  Q.per = per;
+  Q.nwaves = nw;
+  Q.q = d_lineno;
+  Q.nq = n;
+  Q.counts = ws->d_out;
+  Q.prefix = ws->d_in;
+  Q.begin = d_begin;
+  Q.end = d_end;
+  if ((e = hipMemcpyAsync(ws->d_in, ws->h_in, nw * 8, hipMemcpyHostToDevice, st)) != hipSuccess ||
+      (e = launch_spans(Q, st)) != hipSuccess || (e = hipStreamSynchronize(st)) != hipSuccess)
+    return hip_fail(e, "line spans");
+  return UGPU_OK;
 }

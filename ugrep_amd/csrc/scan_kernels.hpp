@@ -343,9 +343,6 @@ struct SpanParams {
 hipError_t launch_sel_summary(const SelParams& S, hipStream_t stream);
 hipError_t launch_sel(const SelParams& S, bool write, hipStream_t stream);
 hipError_t launch_spans(const SpanParams& Q, hipStream_t stream);
-// the wave ranges of the line kernels for a buffer of len bytes (linesel.hip):
-// returns the current device, or -1 with the error recorded
-int line_wave_ranges(uint64_t len, uint64_t* per, uint64_t* nwaves);
 // Boolean line queries, linebool.hip: SelParams for up to 16 match lists and a
 // CNF over them.  The host passes only the lists the formula uses, renumbered
 // from 0, so bit t of a clause mask is list t of these arrays.
