@@ -78,8 +78,10 @@ typedef struct ugpu_dfa_info
                            transducer; UGPU_XI=0 selects dense), 3 xg (gap transducer; UGPU_XG=0),
                            4 wfind (option W, UGPU_PAT_WORD), 5 xc (two-state carry chain; UGPU_XC=0),
                            6 xc U mode (code-point runs without a gap transducer; UGPU_XU=1 prefers it,
-                           UGPU_XU=0 never) */
-  uint32_t contexts;    /* accept contexts per state of the per-context accepts (ugpu_tables_context_host):
+                           UGPU_XU=0 never), 7 ngram (class and wide tables behind an n-gram candidate
+                           filter, e.g. large string sets; UGPU_NG=0 restores kernel 1 / 4; then
+                           prefilter_ppm is the filter's estimate) */
+  uint32_t contexts;   /* accept contexts per state of the per-context accepts (ugpu_tables_context_host):
                            1 = none (no meta edges), 4 = line anchors (bol * 2 + eol), 64 = word boundaries
                            (ugrep_amd/csrc/ctx_bits.hpp) */
   uint32_t shape;       /* UGPU_SHAPE_* bits (the drop-in matcher's test of where the reference's
@@ -94,6 +96,8 @@ typedef struct ugpu_dfa_info
                                      (UGPU_LB=0 disables) */
 #define UGPU_SHAPE_FILTER2 32u /* the sparse kernel's prefilter tests two of a byte's three bit fields: it adds few
                                   candidates for this table (UGPU_FT2=0 / 1 forces it) */
+#define UGPU_SHAPE_NGRAM 64u /* the table scans behind the n-gram candidate filter (kernel 7; UGPU_NG=0 disables;
+                                DESIGN.md 3.1a) */
 
 /* Totals of one scan.  digest = sum(start*31 + len), dcap = sum((start+1)*cap),
    both mod 2^64, start = byte offset + bias. */
@@ -225,6 +229,26 @@ int ugpu_tables_xu_host(const uint32_t *opc, uint32_t nop, uint8_t *tab, uint32_
    (Replaces the reference's position-by-position restart after a failed
    match, lib/matcher.cpp:692-713, for the stitching re-walks.) */
 int ugpu_tables_dom_host(const uint32_t *opc, uint32_t nop, uint32_t *dom, uint32_t dom_cap, uint32_t *n, int *all);
+
+/* Host-only: the n-gram candidate filter of kernel 7 (ugrep_amd/csrc/ngram.hpp,
+   tables.hpp ng_*) under pattern_flags (UGPU_PAT_*): *n = the n-gram length
+   (2-4; 0: the table has none), *log2_bits = log2 of the bitmap's bits, bitmap
+   = its 2^log2_bits / 32 u32 words (NULL: size query; bitmap_cap in words),
+   *ppm = the estimated candidate positions per million on text, *enabled = 1
+   when the plan takes kernel 7 for this table.  Bit ngram_hash(window) is set
+   for every n-byte string that begins a match, so every match start tests
+   positive.  (Replaces the reference's PM4 predictor and advance_pattern_pma,
+   include/reflex/pattern.h:389-401, lib/matcher.cpp:2465-2489.) */
+int ugpu_tables_ngram_host(const uint32_t *opc, uint32_t nop, uint32_t pattern_flags, uint32_t *n,
+                           uint32_t *log2_bits, uint32_t *bitmap, uint32_t bitmap_cap, uint32_t *ppm, int *enabled);
+
+/* Host-only: flags_out[p] = 1 where the n-gram filter, as the device evaluates
+   it over the whole buffer buf[0, len) (the end of the input), makes position
+   p a candidate: p + n <= len and its window tests positive; else 0.  Fails
+   with UGPU_UNSUPPORTED for a table without an n-gram filter.  (The test form
+   of the predictor loop, lib/matcher.cpp:2465-2489.) */
+int ugpu_ngram_candidates_host(const uint32_t *opc, uint32_t nop, uint32_t pattern_flags, const uint8_t *buf,
+                               uint64_t len, uint8_t *flags_out);
 
 /* Host-only: the per-context accept indices of the dense tables (states * 4
    u32: acap[state * 4 + bol * 2 + eol], state numbering as

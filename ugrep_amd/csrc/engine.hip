@@ -104,6 +104,7 @@ struct ugpu_dfa {
   uint32_t* d_lbcls = nullptr;  // 256-bit mask of C
   uint32_t* d_dom = nullptr;    // dominated restarts (tables.hpp dom), or NULL
   uint32_t* d_look = nullptr;   // lookahead TAIL / HEAD masks per state (tables.hpp look), or NULL
+  uint32_t* d_ngram = nullptr;  // the n-gram bitmap (tables.hpp ng_bitmap; ngram_kernel), or NULL
   // idle scanners of ugpu_find_all calls on this table (reused: creating one
   // costs device allocations and property queries)
   std::mutex pool_mu;
@@ -135,6 +136,7 @@ struct ugpu_scanner {
   bool wforce = false;   // (the next scan of a wfast scanner runs wfind_kernel)
   bool xu_exact = false; // U mode: scans run the exact kernel (after a range that flagged UGPU_FLAG_UMIX)
   int word_rec = 0;      // chain records of a wfind scan
+  bool ngram = false;    // word scanners: the passes run ngram_kernel (plan_ngram) in wfind_kernel's place
   bool wxc = false;      // option W on xc_kernel (dfa->xcw), wfind_kernel when it flags UGPU_FLAG_WSLOW
   uint32_t bol0 = 1;     // dbuf[0] begins a line (ugpu_scanner_context; anchored tables)
   size_t smem = 0;       // sparse / dense kernel
@@ -338,6 +340,10 @@ void fill_tables(ScanParams& P, const ugpu_dfa* d)
   P.dom = d->d_dom;
   P.look = d->d_look;
   P.dom_all = d->d_dom && d->t.dom_all ? 1u : 0u;
+  P.ng_bitmap = d->d_ngram;
+  P.ng_n = d->t.ng_n;
+  P.ng_log2 = d->t.ng_log2;
+  P.ng_tab_lds = d->d_ngram && ngram_tab_lds(d->t.format, d->ntrans_pad, d->nwtab, d->t.ng_log2) ? 1u : 0u;
   if (d->lb) P.wstart = 0;  // (the candidates are needle positions, not match starts)
 }
 
@@ -378,7 +384,7 @@ void geometry_for(ScanParams& P, const ugpu_scanner* s, const uint8_t* dbuf, uin
                   uint64_t read_end, uint64_t& off, bool xi = false)
 {
   if (s->word)
-    geometry(P, dbuf, lo, hi, read_end, s->word_rec, wfind_unit(), wfind_waves(), off);
+    geometry(P, dbuf, lo, hi, read_end, s->word_rec, wfind_unit(), s->ngram ? ngram_waves() : wfind_waves(), off);
   else if (xi && s->xc)
     geometry(P, dbuf, lo, hi, read_end, s->xi_rec, xc_unit(s->xu), xc_waves(), off);
   else if (xi && s->xg)
@@ -393,6 +399,7 @@ void geometry_for(ScanParams& P, const ugpu_scanner* s, const uint8_t* dbuf, uin
 
 hipError_t launch_main(const ugpu_scanner* s, const ScanParams& P, bool write, hipStream_t st, bool xi = false)
 {
+  if (s->word && s->ngram) return launch_ngram(P, s->dfa->t.format, write, st);
   if (s->word) return launch_wfind(P, s->dfa->t.format, write, st);
   if (xi && s->xc) return launch_xc(P, write, st);
   if (xi && s->xg) return launch_xg(P, st);
@@ -584,6 +591,15 @@ int ugpu_dfa_create(const uint32_t* opc, uint32_t nop, uint32_t pattern_flags, u
     ugpu_dfa_destroy(d);
     return hip_fail(e, "dominance upload");
   }
+  // the n-gram bitmap, for every table that has one and may take kernel 7
+  // (UGPU_NG is read again when a scanner is created)
+  if (d->t.ng_n >= 2 && d->t.format != FMT_BYTE &&
+      ((e = hipMalloc(&d->d_ngram, d->t.ng_bitmap.size() * 4)) != hipSuccess ||
+       (e = hipMemcpy(d->d_ngram, d->t.ng_bitmap.data(), d->t.ng_bitmap.size() * 4, hipMemcpyHostToDevice)) !=
+           hipSuccess)) {
+    ugpu_dfa_destroy(d);
+    return hip_fail(e, "n-gram bitmap upload");
+  }
   if (d->t.format == FMT_WIDE &&
       ((e = hipMalloc(&d->d_trans32, d->t.trans32.size() * 4)) != hipSuccess ||
        (e = hipMemcpy(d->d_trans32, d->t.trans32.data(), d->t.trans32.size() * 4, hipMemcpyHostToDevice)) !=
@@ -684,6 +700,7 @@ int ugpu_dfa_destroy(ugpu_dfa* d)
   if (d->d_lbcls) (void)hipFree(d->d_lbcls);
   if (d->d_dom) (void)hipFree(d->d_dom);
   if (d->d_look) (void)hipFree(d->d_look);
+  if (d->d_ngram) (void)hipFree(d->d_ngram);
   delete d;
   return UGPU_OK;
 }
@@ -758,7 +775,19 @@ int scanner_create(const ugpu_dfa* dfa, ugpu_scanner** out, bool prefer_write)
   const bool ctx_sparse = dfa->amode && dfa->t.filter && dfa->t.format == FMT_BYTE && !sp_off;
   const bool w_sparse = (dfa->t.filter || dfa->lb || dfa->wsparse) && dfa->t.format == FMT_BYTE && !sp_off;
   // lookahead tables: the lookahead walk (kWalkLook) on wfind_kernel
-  if ((dfa->amode && !ctx_sparse) || dfa->t.format == FMT_WIDE || dfa->t.lookahead ||
+  // n-gram tables (plan_ngram; UGPU_NG=0: off): ngram_kernel on wfind_kernel's
+  // records and passes, whatever kernel the table would take without it
+  const bool ngram = dfa->d_ngram && plan_ngram(dfa->t, dfa->plan);
+  if (ngram) {
+    s->ngram = true;
+    s->word = true;
+    s->word_rec = kMaxRec;
+    if (const char* env = std::getenv("UGPU_MAX_GRID")) {
+      int v = std::atoi(env);
+      if (v >= 1 && v <= kMaxRec) s->word_rec = v;
+    }
+    s->max_rec = s->word_rec;
+  } else if ((dfa->amode && !ctx_sparse) || dfa->t.format == FMT_WIDE || dfa->t.lookahead ||
       (dfa->d_wtab && !dfa->amode && !w_sparse)) {
     const uint32_t nacap = !dfa->amode ? dfa->t.states
                            : dfa->t.ctx_word ? (uint32_t)dfa->t.acap_rows.size() : (uint32_t)dfa->t.acap.size();

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ugpu.h"
+#include "ngram.hpp"
 #include "plan.hpp"
 #include "tables.hpp"
 
@@ -301,6 +302,42 @@ bool plan_filter2(const DfaTables& t, const DfaPlan& p)
   return env && env[0] ? env[0] != '0' : t.filter2;
 }
 
+namespace {
+// the kernel of a COUNT scan without the n-gram kernel
+uint32_t base_kernel(const DfaTables& t, const DfaPlan& p)
+{
+  const char* xenv = std::getenv("UGPU_XI");
+  const char* genv = std::getenv("UGPU_XG");
+  const char* cenv = std::getenv("UGPU_XC");
+  const char* uenv = std::getenv("UGPU_XU");
+  const char* senv = std::getenv("UGPU_SPARSE");
+  const bool byte_filter = (t.filter || p.lb || p.wsparse) && t.format == FMT_BYTE && !(senv && senv[0] == '0');
+  // (dfa_xc and dfa_xu, from the plan instead of the uploaded tables)
+  const bool xc = t.xc && !t.filter && !p.lb && t.cap1 != 0 && (!p.wtab || p.xcw) && !(cenv && cenv[0] == '0');
+  const bool xu = p.xu && (!p.wtab || p.wplus) && !(uenv && uenv[0] == '0');
+  // (context accepts on a prefiltered table: sparse_kernel's context walks)
+  return (p.amode && !byte_filter) || t.format == FMT_WIDE || t.lookahead ||
+                 (p.wtab && !p.wplus && !p.xcw && !byte_filter)
+             ? 4u
+         : byte_filter                                   ? 0u
+         : xc                                            ? 5u
+         : xu                                            ? 6u
+         : (p.xid && !(xenv && xenv[0] == '0'))          ? 2u
+         : (p.xg && !(genv && genv[0] == '0'))           ? 3u
+                                                         : 1u;
+}
+}  // namespace
+
+bool plan_ngram(const DfaTables& t, const DfaPlan& p)
+{
+  const char* env = std::getenv("UGPU_NG");
+  if (env && env[0] == '0') return false;
+  if (t.ng_n < 2 || t.format == FMT_BYTE || p.amode || p.nul || t.lookahead || t.redo || t.start >= t.accb) return false;
+  if (t.ng_density > kNgramBound) return false;
+  const uint32_t k = base_kernel(t, p);
+  return k == 1u || k == 4u;
+}
+
 void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* out)
 {
   ugpu_dfa_info* info = static_cast<ugpu_dfa_info*>(out);
@@ -317,25 +354,12 @@ void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* out)
   info->shape = (t.finite ? UGPU_SHAPE_FINITE : 0u) | (t.word_cond_edges ? UGPU_SHAPE_WORD_COND : 0u) |
                 (t.cap1 != 0 && !t.anchored ? UGPU_SHAPE_ONE_ACCEPT : 0u) | (p.lb ? UGPU_SHAPE_LOOP_NEEDLE : 0u) |
                 (t.lookahead ? UGPU_SHAPE_LOOKAHEAD : 0u) | (plan_filter2(t, p) ? UGPU_SHAPE_FILTER2 : 0u);
-  const char* xenv = std::getenv("UGPU_XI");
-  const char* genv = std::getenv("UGPU_XG");
-  const char* cenv = std::getenv("UGPU_XC");
-  const char* uenv = std::getenv("UGPU_XU");
-  const char* senv = std::getenv("UGPU_SPARSE");
-  const bool byte_filter = (t.filter || p.lb || p.wsparse) && t.format == FMT_BYTE && !(senv && senv[0] == '0');
-  // (dfa_xc and dfa_xu, from the plan instead of the uploaded tables)
-  const bool xc = t.xc && !t.filter && !p.lb && t.cap1 != 0 && (!p.wtab || p.xcw) && !(cenv && cenv[0] == '0');
-  const bool xu = p.xu && (!p.wtab || p.wplus) && !(uenv && uenv[0] == '0');
-  // (context accepts on a prefiltered table: sparse_kernel's context walks)
-  info->kernel = (p.amode && !byte_filter) || t.format == FMT_WIDE || t.lookahead ||
-                         (p.wtab && !p.wplus && !p.xcw && !byte_filter)
-                     ? 4u
-                 : byte_filter                                                                  ? 0u
-                 : xc                                                                           ? 5u
-                 : xu                                                                           ? 6u
-                 : (p.xid && !(xenv && xenv[0] == '0'))                                          ? 2u
-                 : (p.xg && !(genv && genv[0] == '0'))                                           ? 3u
-                                                                                                  : 1u;
+  info->kernel = base_kernel(t, p);
+  if (plan_ngram(t, p)) {
+    info->kernel = 7u;
+    info->shape |= UGPU_SHAPE_NGRAM;
+    info->prefilter_ppm = (uint32_t)(t.ng_density * 1e6) + 1;
+  }
 }
 
 }  // namespace ugpu
@@ -500,6 +524,53 @@ int ugpu_tables_dom_host(const uint32_t* opc, uint32_t nop, uint32_t* dom, uint3
   if (all) *all = t.dom_all ? 1 : 0;
   if (dom && dom_cap < t.dom.size()) return fail(UGPU_INVAL, "dom too small");
   if (dom) std::copy(t.dom.begin(), t.dom.end(), dom);
+  return UGPU_OK;
+}
+
+int ugpu_tables_ngram_host(const uint32_t* opc, uint32_t nop, uint32_t pattern_flags, uint32_t* n, uint32_t* log2_bits,
+                           uint32_t* bitmap, uint32_t bitmap_cap, uint32_t* ppm, int* enabled)
+{
+  if (!n || !log2_bits) return fail(UGPU_INVAL, "NULL argument");
+  if (pattern_flags & ~(UGPU_PAT_WORD | UGPU_PAT_EMPTY)) return fail(UGPU_INVAL, "unknown pattern flags");
+  DfaTables t;
+  std::string err;
+  const int rc = build_tables(opc, nop, t, err);
+  if (rc != 0) return fail(rc == 1 ? UGPU_UNSUPPORTED : UGPU_INVAL, err);
+  *n = t.ng_n;
+  *log2_bits = t.ng_n ? t.ng_log2 : 0u;
+  if (ppm) *ppm = t.ng_n ? (uint32_t)(t.ng_density * 1e6) + 1 : 0u;
+  if (enabled) {
+    const DfaPlan pl = dfa_plan(t, pattern_flags);
+    *enabled = pl.ok && plan_ngram(t, pl) ? 1 : 0;
+  }
+  if (bitmap && t.ng_n) {
+    if (bitmap_cap < t.ng_bitmap.size()) return fail(UGPU_CAPACITY, "bitmap capacity");
+    std::copy(t.ng_bitmap.begin(), t.ng_bitmap.end(), bitmap);
+  }
+  return UGPU_OK;
+}
+
+int ugpu_ngram_candidates_host(const uint32_t* opc, uint32_t nop, uint32_t pattern_flags, const uint8_t* buf,
+                               uint64_t len, uint8_t* flags_out)
+{
+  if ((!buf || !flags_out) && len) return fail(UGPU_INVAL, "NULL argument");
+  if (pattern_flags & ~(UGPU_PAT_WORD | UGPU_PAT_EMPTY)) return fail(UGPU_INVAL, "unknown pattern flags");
+  DfaTables t;
+  std::string err;
+  const int rc = build_tables(opc, nop, t, err);
+  if (rc != 0) return fail(rc == 1 ? UGPU_UNSUPPORTED : UGPU_INVAL, err);
+  if (!t.ng_n) return fail(UGPU_UNSUPPORTED, "the table has no n-gram filter");
+  const uint32_t mask = ngram_mask(t.ng_n);
+  for (uint64_t p = 0; p < len; ++p) {
+    // (the device's rule: a window must lie inside the readable bytes)
+    uint8_t f = 0;
+    if (p + t.ng_n <= len) {
+      uint32_t w = 0;
+      for (uint32_t i = 0; i < t.ng_n; ++i) w |= (uint32_t)buf[p + i] << (8 * i);
+      f = ngram_test(t.ng_bitmap.data(), w & mask, t.ng_log2) ? 1 : 0;
+    }
+    flags_out[p] = f;
+  }
   return UGPU_OK;
 }
 

@@ -50,6 +50,12 @@ DfaPlan dfa_plan(const DfaTables& t, uint32_t flags, int lb = -1);
 // first-byte prefilter walked by the plain walk (no loop needle, option W or
 // context accepts).  UGPU_FT2=0 / 1, read per call, forces it off / on there.
 bool plan_filter2(const DfaTables& t, const DfaPlan& p);
+// The n-gram kernel (kernel 7, ngram_kernel.hip; tables.hpp ng_*): a class or
+// wide table without context accepts, lookahead, REDO or option N that would
+// otherwise scan on dense_kernel (kernel 1) or, for being wide or under option
+// W, on wfind_kernel (kernel 4), and whose filter is selective
+// (ng_density <= kNgramBound).  UGPU_NG=0, read per call, turns it off.
+bool plan_ngram(const DfaTables& t, const DfaPlan& p);
 // ugpu_dfa_info from the tables and the plan (ugpu_dfa_plan_host, ugpu_dfa_info_get)
 void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* info /* ugpu_dfa_info* */);
 // \w+ as ugpu_compile builds it

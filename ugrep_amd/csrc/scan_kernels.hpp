@@ -248,6 +248,10 @@ struct ScanParams {
   // suspended state; NULL: walks complete in their lanes (option W)
   uint32_t* susp;
   SuspRec* srec;
+  // ngram_kernel: the hashed n-gram bitmap (ngram.hpp; 2^ng_log2 bits), the
+  // n-gram length, and whether the kernel stages the class table in LDS
+  const uint32_t* ng_bitmap;
+  uint32_t ng_n, ng_log2, ng_tab_lds;
 };
 
 // Forest FIND (forest.hip): exact for every table, no resynchronisation
@@ -394,6 +398,13 @@ hipError_t launch_wfind(const ScanParams& P, uint32_t format, bool write, hipStr
 uint32_t wfind_unit();
 uint32_t wfind_waves();
 size_t wfind_smem_bytes(uint32_t ntrans_pad, uint32_t nstates, uint32_t nwtab, uint32_t nacap, uint32_t nmap);
+// n-gram candidate kernel, ngram_kernel.hip: wfind_kernel's records (one per
+// wave, kWaveTile tiles, stitched by fix_kernel), candidates from the hashed
+// n-gram bitmap walked with the plain or the option-W walk (P.wtab); COUNT and
+// OFFSETS passes.  ngram_tab_lds: whether a class table is staged in LDS
+hipError_t launch_ngram(const ScanParams& P, uint32_t format, bool write, hipStream_t stream);
+uint32_t ngram_waves();
+bool ngram_tab_lds(uint32_t format, uint32_t ntrans_pad, uint32_t nwtab, uint32_t ng_log2);
 // immediate-transducer kernel, xi_kernel.hip (COUNT mode only)
 hipError_t launch_xi(const ScanParams& P, size_t smem, hipStream_t stream);
 hipError_t xi_occupancy(size_t smem, int* blocks_per_cu);

@@ -10,6 +10,7 @@
 // then gotos in descending lo order; the interpreter takes the first goto whose
 // [lo,hi] holds the byte (lib/matcher.cpp:467-502).
 #include "tables.hpp"
+#include "ngram.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -1163,8 +1164,105 @@ int build_tables(const uint32_t* opc, uint32_t nop, DfaTables& out, std::string&
     t.xc = false;
     t.xu = false;
   }
+  if (!look && !anchored && !redo) build_ngram(t);
   out = std::move(t);
   return 0;
+}
+
+// The n-gram filter (tables.hpp ng_*, ngram.hpp): the table's paths of depth
+// n from the start state, hashed into a bitmap.
+void build_ngram(DfaTables& t)
+{
+  t.ng_n = 0;
+  if (t.format == FMT_BYTE || t.accepting == 0 || t.start >= t.accb || t.start_acc) return;
+  const uint32_t R = t.row;
+  // the bytes of each column (the enumeration walks columns, then expands them)
+  std::vector<std::vector<uint8_t>> colbytes(R);
+  for (uint32_t b = 0; b < 256; ++b) colbytes[t.cls[b]].push_back((uint8_t)b);
+  auto next = [&](uint32_t e, uint32_t col) -> uint32_t {
+    return t.format == FMT_WIDE ? t.trans32[(size_t)e + col] : (uint32_t)t.trans[(size_t)e + col];
+  };
+  // shortest match: breadth-first depth of the first accepting state (up to kNgMaxN)
+  uint32_t shortest = 0;
+  {
+    std::vector<uint8_t> seen(t.states, 0);
+    std::vector<uint32_t> cur{t.start}, nxt;
+    seen[t.start / R] = 1;
+    for (uint32_t d = 1; d <= kNgMaxN && !shortest && !cur.empty(); ++d) {
+      nxt.clear();
+      for (uint32_t e : cur)
+        for (uint32_t c = 0; c < R && !shortest; ++c) {
+          if (colbytes[c].empty()) continue;
+          const uint32_t e2 = next(e, c);
+          if (!e2) continue;
+          if (e2 >= t.accb) shortest = d;
+          if (!seen[e2 / R]) seen[e2 / R] = 1, nxt.push_back(e2);
+        }
+      cur.swap(nxt);
+    }
+    if (!shortest) shortest = kNgMaxN;  // (no accept within kNgMaxN bytes)
+  }
+  for (uint32_t n = std::min(shortest, kNgMaxN); n >= 2; --n) {
+    // depth-first over (entry, window so far); gives up above kNgMaxGrams
+    std::vector<uint32_t> grams;
+    bool over = false;
+    struct Node {
+      uint32_t e, w, d;
+    };
+    std::vector<Node> stack{{t.start, 0u, 0u}};
+    while (!stack.empty() && !over) {
+      const Node nd = stack.back();
+      stack.pop_back();
+      for (uint32_t c = 0; c < R && !over; ++c) {
+        if (colbytes[c].empty()) continue;
+        const uint32_t e2 = next(nd.e, c);
+        if (!e2) continue;
+        for (uint8_t b : colbytes[c]) {
+          const uint32_t w = nd.w | ((uint32_t)b << (8 * nd.d));
+          if (nd.d + 1 == n) {
+            if (grams.size() >= kNgMaxGrams) {
+              over = true;
+              break;
+            }
+            grams.push_back(w);
+          } else {
+            if (stack.size() >= 4 * (size_t)kNgMaxGrams) {
+              over = true;
+              break;
+            }
+            stack.push_back({e2, w, nd.d + 1});
+          }
+        }
+      }
+    }
+    if (over || grams.empty()) continue;
+    // the smallest bitmap that stays under 1/256 full (kNgMaxLog2 at most:
+    // the largest sets fill it further, which ng_density accounts for)
+    uint32_t k = kNgMinLog2;
+    while (k < kNgMaxLog2 && ((uint64_t)grams.size() << 8) > (1ull << k)) ++k;
+    t.ng_bitmap.assign((size_t)1 << (k - 5), 0u);
+    uint64_t text = 0;
+    for (uint32_t w : grams) {
+      const uint32_t h = ngram_hash(w, k);
+      t.ng_bitmap[h >> 5] |= 1u << (h & 31u);
+      bool tx = true;
+      for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t b = (w >> (8 * i)) & 255u;
+        tx = tx && (b == '\n' || (b >= 0x20 && b < 0x7f));
+      }
+      text += tx ? 1u : 0u;
+    }
+    uint64_t set = 0;
+    for (uint32_t v : t.ng_bitmap) set += (uint64_t)__builtin_popcount(v);
+    t.ng_n = n;
+    t.ng_log2 = k;
+    t.ng_grams = (uint32_t)grams.size();
+    t.ng_fill = (double)set / (double)(1ull << k);
+    double all = 1.0;
+    for (uint32_t i = 0; i < n; ++i) all *= 96.0;
+    t.ng_density = std::min(1.0, (double)text / all + t.ng_fill);
+    return;
+  }
 }
 
 // Loop-needle tables (host_api.cpp loop_needle): the prefilter looks for the

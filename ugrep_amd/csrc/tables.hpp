@@ -176,7 +176,31 @@ struct DfaTables {
   std::vector<uint32_t> look;
   bool lookahead = false;
   std::vector<uint32_t> acap;  // states * 4, or states * 64 (ctx_word)
+  // N-gram candidate filter (ngram.hpp; ngram_kernel.hip), for class and wide
+  // tables without context accepts, lookahead or REDO whose start state does
+  // not accept.  Replaces, for large string sets, the reference's PM4
+  // predictor and advance_pattern_pma (include/reflex/pattern.h:389-401,
+  // lib/matcher.cpp:2465-2489).  ng_n = 0: the table does not qualify (a
+  // 1-byte match, or too many n-grams for every n >= 2).
+  // ng_density: the estimated candidate fraction on text, i.e. the share of
+  // all text n-grams (printable ASCII and '\n', uniform, as Bucket::density)
+  // that are in G, plus the bitmap's fill ratio (non-members hash to set bits
+  // at about that rate).
+  uint32_t ng_n = 0, ng_log2 = 0, ng_grams = 0;
+  std::vector<uint32_t> ng_bitmap;  // 2^ng_log2 bits
+  double ng_density = 1.0, ng_fill = 1.0;
 };
+
+// Largest estimated candidate fraction (ng_density) at which a table takes the
+// n-gram kernel.  Measured (tools/bench_wordset.py, profiles/wordset_ab.json:
+// 4-byte prefixes of a 100-word set planted in 1 GiB of the C2 corpus, COUNT
+// scans against dense_kernel): 1.30x faster at a candidate fraction of 0.10,
+// level at 0.146 (5.92 against 6.00 ms), 0.81x at 0.20; against wfind_kernel
+// (option W) still 3.4x faster at 0.20.  The bound is the last density
+// measured clearly ahead of dense_kernel.
+constexpr double kNgramBound = 0.10;
+// builds the ng_* fields of a finished table (called by build_tables)
+void build_ngram(DfaTables& t);
 
 // (context bits CTX_*: ctx_bits.hpp)
 

@@ -188,6 +188,39 @@ def host_dom(opc, want_all=False):
     return (bits, bool(al.value)) if want_all else bits
 
 
+def host_ngram(opc, word=False):
+    """The n-gram candidate filter of kernel 7 (ngram.hpp, ugpu_tables_ngram_host),
+    built on the host: dict(n, log2_bits, bitmap uint32[2^log2_bits / 32], ppm,
+    fill, enabled), or None when the table has none.  ppm = the estimated
+    candidate positions per million on text, fill = the bitmap's share of set
+    bits, enabled = the plan takes kernel 7 under `word`."""
+    a, p = _as_u32(compile_regex(opc) if isinstance(opc, (str, bytes)) else opc)
+    fl = PAT_WORD if word else 0
+    n, k, ppm, en = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int()
+    check(lib.ugpu_tables_ngram_host(p, len(a), fl, ctypes.byref(n), ctypes.byref(k), None, 0, ctypes.byref(ppm),
+                                     ctypes.byref(en)))
+    if not n.value:
+        return None
+    bm = np.zeros((1 << k.value) // 32, np.uint32)
+    check(lib.ugpu_tables_ngram_host(p, len(a), fl, ctypes.byref(n), ctypes.byref(k), bm.ctypes.data_as(_lib.c_u32p),
+                                     len(bm), ctypes.byref(ppm), ctypes.byref(en)))
+    fill = float(np.unpackbits(bm.view(np.uint8)).sum()) / float(1 << k.value)
+    return dict(n=n.value, log2_bits=k.value, bitmap=bm, ppm=ppm.value, fill=fill, enabled=bool(en.value))
+
+
+def host_ngram_candidates(opc, data, word=False):
+    """uint8[len(data)]: 1 where the n-gram filter, as the device evaluates it
+    over the whole buffer, makes the position a candidate
+    (ugpu_ngram_candidates_host)."""
+    a, p = _as_u32(compile_regex(opc) if isinstance(opc, (str, bytes)) else opc)
+    buf = np.ascontiguousarray(np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                               dtype=np.uint8)
+    out = np.zeros(len(buf), np.uint8)
+    check(lib.ugpu_ngram_candidates_host(p, len(a), PAT_WORD if word else 0, buf.ctypes.data_as(_lib.c_u8p), len(buf),
+                                         out.ctypes.data_as(_lib.c_u8p)))
+    return out
+
+
 class Pattern:
     """Compiled pattern (opcode words) with its device tables."""
 
