@@ -510,6 +510,81 @@ int ugpu_select_lines_bool(const uint8_t *dbuf, uint64_t len, const uint64_t *co
    and word boundaries consume no byte and do not count). */
 int ugpu_tables_newline_host(const uint32_t *opc, uint32_t nop, int *nl);
 
+/* --- batched FIND: many inputs in one scan, with per-input records ---
+   Replaces the per-file loop of the reference (src/ugrep.cpp:4261-4480, one
+   job per file: each file gets its own matcher pass, its own line counter and
+   its own totals) for inputs that are already in memory: the fixed cost of a
+   FIND pass (an input copy, the launches, the host round trips, a result copy)
+   is paid once per batch instead of once per file.
+
+   The inputs are packed back to back into one buffer, each ended by '\n' (one
+   is added to a non-empty input that lacks it; an empty input takes no bytes).
+   When no match of the table can contain '\n', the FIND chain of the packed
+   buffer passes through every input's first byte and its match list is the
+   concatenation of the per-input lists: at_wb reads a preceding '\n' like the
+   buffer begin, at_we and at_eol read a following '\n' like EOF, and bol after
+   '\n' equals bol at the begin.  One exception: an input that
+   ends in a bare '\r' -- at_eol is 0 for '\r' then EOF but 1 for "\r\n". */
+
+/* Host-only: *one_scan = 1 when a batch on this table can be served by one
+   scan of the packed buffer: the table is one ugpu_dfa_plan_host accepts, no
+   match can contain '\n' (ugpu_tables_newline_host), and pattern_flags has no
+   UGPU_PAT_EMPTY (option N's "never at the end of the input" is a per-input
+   rule).  Returns what ugpu_dfa_plan_host returns. */
+int ugpu_batch_plan_host(const uint32_t *opc, uint32_t nop, uint32_t pattern_flags, int *one_scan);
+
+/* Cut a sorted device match list (as ugpu_scan_offsets writes it) at nseg + 1
+   ascending device offsets d_bounds (the last <= len) into per-segment
+   results; same buffer rules as ugpu_lines.  Segment s is [bounds[s],
+   bounds[s+1]); empty segments, and runs of them, are allowed.  d_first[s]
+   (nseg + 1 entries) = index of the first record with start >= bounds[s]:
+   segment s owns the records [first[s], first[s+1]); records before bounds[0]
+   or at or after bounds[nseg] belong to no segment (their rel and line are 0).
+   d_cap NULL: every record has accept index cap1; d_len NULL: all lengths 0.
+   Per record: d_rel = start - bounds[s], d_line = 1 + the number of '\n' in
+   [bounds[s], start) (either array may be NULL).  Per segment: d_digest =
+   sum(rel*31 + len) and d_dcap = sum((rel+1)*cap) mod 2^64 (ugpu_totals'
+   definitions with the segment's own offsets), d_newlines = the number of '\n'
+   in the segment, d_mlines = the number of distinct line values among its
+   records (matching_lines of ugpu_lines over that segment alone).  Integer
+   sums only: results repeat exactly from run to run.  Synchronous. */
+int ugpu_split_matches(const uint8_t *dbuf, uint64_t len, const uint64_t *d_bounds, uint32_t nseg,
+                       const uint64_t *d_start, const uint32_t *d_len, const uint32_t *d_cap, uint32_t cap1, uint64_t n,
+                       uint64_t *d_first, uint64_t *d_digest, uint64_t *d_dcap, uint64_t *d_newlines,
+                       uint64_t *d_mlines, uint64_t *d_rel, uint64_t *d_line, void *stream);
+
+/* FIND over ninputs host buffers.  For every input i, (count, digest, dcap,
+   records) equal ugpu_find_all(dfa, bufs[i], lens[i], 0, mode), and newlines,
+   matching_lines and line equal ugpu_lines over that input alone (the added
+   separator does not count) -- for every table ugpu_dfa_create accepts; only
+   the cost differs.  The inputs are packed into pinned memory and go to the
+   device in one copy per sub-batch of at most UGPU_BATCH_BYTES packed bytes
+   (environment, read at each call; default 1 GiB; a sub-batch is cut only
+   between inputs, a larger input is a sub-batch by itself).  A sub-batch is
+   served by one scan of the packed buffer plus ugpu_split_matches when
+   ugpu_batch_plan_host allows it and not both hold: the table has per-context
+   accepts (ugpu_dfa_info.contexts != 1) and some input of the sub-batch ends
+   in a bare '\r'.  Otherwise each input is scanned by itself over its range of
+   the packed copy, and the same split lays the result out.  flags has
+   UGPU_BATCH_ONE_SCAN when no sub-batch took the per-input route.  COUNT mode
+   skips the record arrays (start, len, cap, line are NULL).  ninputs == 0
+   gives an empty result; a NULL bufs[i] with lens[i] > 0 gives UGPU_INVAL.
+   Synchronous. */
+#define UGPU_BATCH_ONE_SCAN 1u
+typedef struct ugpu_batch_result
+{
+  uint32_t ninputs, flags;
+  uint64_t count;                                        /* all inputs */
+  uint64_t *first;                                       /* ninputs + 1: input i's records are [first[i], first[i+1]) */
+  uint64_t *digest, *dcap, *newlines, *matching_lines;   /* ninputs each */
+  uint64_t *start;                                       /* count each; start is relative to its input */
+  uint32_t *len, *cap;
+  uint64_t *line;                                        /* 1-based line within its input */
+} ugpu_batch_result;
+int ugpu_find_batch(const ugpu_dfa *dfa, const uint8_t *const *bufs, const uint64_t *lens, uint32_t ninputs,
+                    uint32_t mode, ugpu_batch_result **out);
+int ugpu_batch_free(ugpu_batch_result *r);
+
 /* --- binary-file detection ---
    Device buffers of any alignment (the kernel reads the enclosing 16-byte
    granules).  Synchronous. */

@@ -32,6 +32,7 @@ BIN_NULL_DATA, BIN_NUL_ONLY, BIN_INIT_WINDOW = 1, 2, 4
 SEL_INVERT = 1
 BOOL_FILES = 2
 BOOL_MAX_LISTS, BOOL_MAX_CLAUSES = 16, 64
+BATCH_ONE_SCAN = 1
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u16p = ctypes.POINTER(ctypes.c_uint16)
@@ -54,6 +55,12 @@ class Totals(ctypes.Structure):
 class Result(ctypes.Structure):
     _fields_ = [("count", ctypes.c_uint64), ("digest", ctypes.c_uint64), ("dcap", ctypes.c_uint64),
                 ("start", c_u64p), ("len", c_u32p), ("cap", c_u32p)]
+
+
+class BatchResult(ctypes.Structure):
+    _fields_ = [("ninputs", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("count", ctypes.c_uint64),
+                ("first", c_u64p), ("digest", c_u64p), ("dcap", c_u64p), ("newlines", c_u64p),
+                ("matching_lines", c_u64p), ("start", c_u64p), ("len", c_u32p), ("cap", c_u32p), ("line", c_u64p)]
 
 
 class BoolClause(ctypes.Structure):
@@ -152,6 +159,11 @@ def _load():
                                                   ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64),
                                                   P(ctypes.c_int), V]),
         "ugpu_tables_newline_host": (ctypes.c_int, [c_u32p, ctypes.c_uint32, P(ctypes.c_int)]),
+        "ugpu_batch_plan_host": (ctypes.c_int, [c_u32p, ctypes.c_uint32, ctypes.c_uint32, P(ctypes.c_int)]),
+        "ugpu_split_matches": (ctypes.c_int, [V, ctypes.c_uint64, V, ctypes.c_uint32, V, V, V, ctypes.c_uint32,
+                                              ctypes.c_uint64, V, V, V, V, V, V, V, V]),
+        "ugpu_find_batch": (ctypes.c_int, [V, P(V), c_u64p, ctypes.c_uint32, ctypes.c_uint32, P(P(BatchResult))]),
+        "ugpu_batch_free": (ctypes.c_int, [P(BatchResult)]),
         "ugpu_check_utf8": (ctypes.c_int, [V, ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_find_nul": (ctypes.c_int, [V, ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_is_binary": (ctypes.c_int, [V, ctypes.c_uint64, ctypes.c_uint32, P(ctypes.c_int), V]),

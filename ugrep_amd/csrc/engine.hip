@@ -116,6 +116,8 @@ struct ugpu_dfa {
   uint32_t pflags = 0;
   std::mutex rep_mu;
   std::vector<ugpu_dfa*> reps;
+  // ugpu_batch_plan_host's answer for this table (-1: not asked yet)
+  std::atomic<int> batch_one{-1};
 };
 
 struct ugpu_scanner {
@@ -1355,6 +1357,11 @@ struct FindWs {
   uint32_t* d_len = nullptr;
   uint32_t* d_cap = nullptr;
   uint64_t out_cap = 0;
+  // ugpu_find_batch: the per-input arrays of ugpu_split_matches, and its rel / line
+  uint64_t* d_seg = nullptr;
+  uint64_t seg_cap = 0;  // values
+  uint64_t* d_rl = nullptr;
+  uint64_t rl_cap = 0;   // records (two arrays)
 
   hipError_t reserve_in(uint64_t n)
   {
@@ -1382,6 +1389,45 @@ struct FindWs {
         (e = hipMalloc(&d_cap, c * 4)) != hipSuccess)
       return e;
     out_cap = c;
+    return hipSuccess;
+  }
+  // reserve_out that keeps the first `keep` records
+  hipError_t reserve_out_keep(uint64_t n, uint64_t keep)
+  {
+    if (n <= out_cap) return hipSuccess;
+    if (!keep) return reserve_out(n);
+    uint64_t* os = d_start;
+    uint32_t *ol = d_len, *oc = d_cap;
+    d_start = nullptr;
+    d_len = d_cap = nullptr;
+    out_cap = 0;
+    hipError_t e = reserve_out(n + n / 2);  // (grows by halves: few copies over a sub-batch)
+    if (e == hipSuccess) e = hipMemcpyAsync(d_start, os, keep * 8, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_len, ol, keep * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_cap, oc, keep * 4, hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(os);
+    (void)hipFree(ol);
+    (void)hipFree(oc);
+    return e;
+  }
+  hipError_t reserve_batch(uint64_t seg, uint64_t n)
+  {
+    hipError_t e;
+    if (seg > seg_cap) {
+      (void)hipFree(d_seg);
+      d_seg = nullptr;
+      seg_cap = 0;
+      if ((e = hipMalloc(&d_seg, (seg + seg / 4) * 8)) != hipSuccess) return e;
+      seg_cap = seg + seg / 4;
+    }
+    if (n > rl_cap) {
+      (void)hipFree(d_rl);
+      d_rl = nullptr;
+      rl_cap = 0;
+      if ((e = hipMalloc(&d_rl, (n + n / 4) * 16)) != hipSuccess) return e;
+      rl_cap = n + n / 4;
+    }
     return hipSuccess;
   }
 };
@@ -3202,3 +3248,218 @@ int ugpu_gen(int kind, uint64_t seed, uint64_t off, uint8_t* dbuf, uint64_t len,
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- batched FIND
+namespace {
+
+uint64_t batch_packed_len(const uint8_t* b, uint64_t n) { return n ? n + (b[n - 1] != '\n' ? 1u : 0u) : 0; }
+
+template <class T>
+bool batch_grow(T*& a, uint64_t n)
+{
+  void* p = std::realloc(a, (n ? n : 1) * sizeof(T));
+  if (!p) return false;
+  a = static_cast<T*>(p);
+  return true;
+}
+
+// One sub-batch: inputs [i0, i1), `total` packed bytes (> 0).  Appends the
+// records at r->count and fills the per-input arrays; *one is whether it was
+// served by one scan.
+int batch_sub(const ugpu_dfa* dfa, ugpu_scanner* s, FindWs* ws, bool table_one, uint32_t contexts,
+              const uint8_t* const* bufs, const uint64_t* lens, uint32_t i0, uint32_t i1, uint64_t total, uint32_t mode,
+              ugpu_batch_result* r, bool* one)
+{
+  const uint32_t nseg = i1 - i0;
+  const uint64_t nb = (uint64_t)nseg + 1, nout = 5ull * nseg + 1;
+  const uint64_t pad = (total + 15) & ~15ull;  // the bounds follow the bytes: one H2D copy for both
+  size_t got = 0;
+  uint8_t* pin = pinned_get(pad + (nb + nout) * 8, got);
+  if (!pin) return fail(UGPU_NOMEM, "pinned batch block");
+  uint64_t* bounds = reinterpret_cast<uint64_t*>(pin + pad);
+  uint64_t* hout = bounds + nb;
+  uint64_t off = 0;
+  bool bare_cr = false;
+  for (uint32_t k = 0; k < nseg; ++k) {
+    const uint8_t* b = bufs[i0 + k];
+    const uint64_t n = lens[i0 + k];
+    bounds[k] = off;
+    if (!n) continue;
+    std::memcpy(pin + off, b, n);
+    off += n;
+    if (b[n - 1] != '\n') pin[off++] = '\n';
+    bare_cr = bare_cr || b[n - 1] == '\r';
+  }
+  bounds[nseg] = off;  // == total
+  std::memset(pin + off, 0, pad - off);
+  *one = table_one && !(contexts != 1 && bare_cr);
+  hipError_t e;
+  int rc = UGPU_OK;
+  if ((e = ws->reserve_in(pad + nb * 8)) != hipSuccess ||
+      (e = hipMemcpyAsync(ws->d_in, pin, pad + nb * 8, hipMemcpyHostToDevice, ws->st)) != hipSuccess)
+    rc = hip_fail(e, "batch input copy");
+  const uint64_t* d_bounds = reinterpret_cast<const uint64_t*>(ws->d_in + pad);
+  // records are always written on the device: the split needs them
+  uint64_t n = 0;
+  ugpu_totals tot{};
+  if (!rc && *one) {
+    s->stage_once = true;
+    rc = ugpu_scan(s, ws->d_in, 0, total, total, 1, 0, ws->st);
+    if (!rc) rc = ugpu_scan_totals(s, &tot);
+    n = tot.count;
+    if (!rc && n) {
+      if ((e = ws->reserve_out(n)) != hipSuccess)
+        rc = hip_fail(e, "match list");
+      else
+        rc = ugpu_scan_offsets(s, ws->d_start, ws->d_len, ws->d_cap, n, ws->st);
+    }
+  } else if (!rc) {
+    // each input with its own whole-input semantics: its bytes of the packed
+    // copy as a buffer of their own, the records biased to packed offsets
+    for (uint32_t k = 0; k < nseg && !rc; ++k) {
+      const uint64_t len = lens[i0 + k];
+      if (!len) continue;
+      s->stage_once = true;
+      rc = ugpu_scan(s, ws->d_in + bounds[k], 0, len, len, 1, bounds[k], ws->st);
+      if (!rc) rc = ugpu_scan_totals(s, &tot);
+      if (rc || !tot.count) continue;
+      if ((e = ws->reserve_out_keep(n + tot.count, n)) != hipSuccess)
+        rc = hip_fail(e, "match list");
+      else
+        rc = ugpu_scan_offsets(s, ws->d_start + n, ws->d_len + n, ws->d_cap + n, tot.count, ws->st);
+      n += tot.count;
+    }
+  }
+  if (!rc && (e = ws->reserve_batch(nout, n)) != hipSuccess) rc = hip_fail(e, "batch arrays");
+  uint64_t* d_first = ws->d_seg;
+  uint64_t* d_per = ws->d_seg + nb;  // digest, dcap, newlines, mlines: nseg each
+  uint64_t* d_rel = ws->d_rl;
+  uint64_t* d_line = ws->d_rl ? ws->d_rl + n : nullptr;
+  const bool recs = mode == UGPU_MODE_OFFSETS && n > 0;
+  if (!rc)
+    rc = ugpu_split_matches(ws->d_in, total, d_bounds, nseg, ws->d_start, ws->d_len, ws->d_cap, 0, n, d_first, d_per,
+                            d_per + nseg, d_per + 2ull * nseg, d_per + 3ull * nseg, recs ? d_rel : nullptr,
+                            recs ? d_line : nullptr, ws->st);
+  const uint64_t base = r->count;
+  if (!rc && recs &&
+      !(batch_grow(r->start, base + n) && batch_grow(r->len, base + n) && batch_grow(r->cap, base + n) &&
+        batch_grow(r->line, base + n)))
+    rc = fail(UGPU_NOMEM, "match list allocation");
+  if (!rc && ((e = hipMemcpyAsync(hout, ws->d_seg, nout * 8, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
+              (recs && ((e = hipMemcpyAsync(r->start + base, d_rel, n * 8, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
+                        (e = hipMemcpyAsync(r->len + base, ws->d_len, n * 4, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
+                        (e = hipMemcpyAsync(r->cap + base, ws->d_cap, n * 4, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
+                        (e = hipMemcpyAsync(r->line + base, d_line, n * 8, hipMemcpyDeviceToHost, ws->st)) != hipSuccess))))
+    rc = hip_fail(e, "batch result copy");
+  if ((e = hipStreamSynchronize(ws->st)) != hipSuccess && !rc) rc = hip_fail(e, "batch result copy");
+  if (!rc) {
+    const uint64_t* hper = hout + nb;
+    for (uint32_t k = 0; k < nseg; ++k) {
+      r->first[i0 + k] = base + hout[k];
+      r->digest[i0 + k] = hper[k];
+      r->dcap[i0 + k] = hper[nseg + k];
+      // the separator that was added does not count
+      const uint64_t len = lens[i0 + k];
+      r->newlines[i0 + k] = hper[2ull * nseg + k] - (len && bufs[i0 + k][len - 1] != '\n' ? 1u : 0u);
+      r->matching_lines[i0 + k] = hper[3ull * nseg + k];
+    }
+    r->count = base + n;
+  }
+  pinned_put(pin, got);
+  return rc;
+}
+
+}  // namespace
+
+int ugpu_batch_free(ugpu_batch_result* r)
+{
+  if (!r) return UGPU_OK;
+  std::free(r->first);
+  std::free(r->digest);
+  std::free(r->dcap);
+  std::free(r->newlines);
+  std::free(r->matching_lines);
+  std::free(r->start);
+  std::free(r->len);
+  std::free(r->cap);
+  std::free(r->line);
+  std::free(r);
+  return UGPU_OK;
+}
+
+int ugpu_find_batch(const ugpu_dfa* dfa, const uint8_t* const* bufs, const uint64_t* lens, uint32_t ninputs,
+                    uint32_t mode, ugpu_batch_result** out)
+{
+  if (!dfa || !out || (ninputs && (!bufs || !lens))) return fail(UGPU_INVAL, "NULL argument");
+  *out = nullptr;
+  for (uint32_t i = 0; i < ninputs; ++i)
+    if (!bufs[i] && lens[i]) return fail(UGPU_INVAL, "NULL input with a length");
+  int one = dfa->batch_one.load(std::memory_order_relaxed);
+  if (one < 0) {
+    const int rc = ugpu_batch_plan_host(dfa->opc.data(), (uint32_t)dfa->opc.size(), dfa->pflags, &one);
+    if (rc) return rc;
+    const_cast<ugpu_dfa*>(dfa)->batch_one.store(one, std::memory_order_relaxed);
+  }
+  ugpu_dfa_info info;
+  int rc = ugpu_dfa_info_get(dfa, &info);
+  if (rc) return rc;
+  ugpu_batch_result* r = static_cast<ugpu_batch_result*>(std::calloc(1, sizeof(ugpu_batch_result)));
+  if (!r) return fail(UGPU_NOMEM, "host allocation");
+  r->ninputs = ninputs;
+  const uint64_t na = (uint64_t)ninputs + 1;
+  r->first = static_cast<uint64_t*>(std::calloc(na, 8));
+  r->digest = static_cast<uint64_t*>(std::calloc(na, 8));
+  r->dcap = static_cast<uint64_t*>(std::calloc(na, 8));
+  r->newlines = static_cast<uint64_t*>(std::calloc(na, 8));
+  r->matching_lines = static_cast<uint64_t*>(std::calloc(na, 8));
+  if (!r->first || !r->digest || !r->dcap || !r->newlines || !r->matching_lines) {
+    ugpu_batch_free(r);
+    return fail(UGPU_NOMEM, "host allocation");
+  }
+  bool all_one = one != 0;
+  uint64_t limit = env_u64("UGPU_BATCH_BYTES", 1ull << 30);
+  if (!limit) limit = 1;
+  ugpu_scanner* s = nullptr;
+  FindWs* ws = nullptr;
+  for (uint32_t i = 0; i < ninputs && !rc;) {
+    // the next sub-batch: cut only between inputs, a larger input by itself
+    uint32_t j = i;
+    uint64_t total = 0;
+    for (; j < ninputs; ++j) {
+      const uint64_t pl = batch_packed_len(bufs[j], lens[j]);
+      if (j > i && total + pl > limit) break;
+      total += pl;
+    }
+    if (!total) {  // empty inputs only
+      for (uint32_t k = i; k < j; ++k) r->first[k] = r->count;
+      i = j;
+      continue;
+    }
+    if (!ws) {  // (the calling thread's device: the table copy there, ugpu_select_device)
+      int dev = 0;
+      const hipError_t e = hipGetDevice(&dev);
+      if (e != hipSuccess) rc = hip_fail(e, "hipGetDevice");
+      if (!rc) rc = dfa_on(dfa, dev, &dfa);
+      if (!rc) rc = scanner_acquire(dfa, &s, true);
+      if (!rc && !(ws = find_ws_acquire(dev))) rc = fail(UGPU_NOMEM, "find workspace");
+      if (rc) break;
+    }
+    bool sub_one = false;
+    rc = batch_sub(dfa, s, ws, one != 0, info.contexts, bufs, lens, i, j, total, mode, r, &sub_one);
+    all_one = all_one && sub_one;
+    i = j;
+  }
+  if (ws) {
+    (void)hipStreamSynchronize(ws->st);
+    find_ws_release(ws);
+  }
+  if (s) scanner_release(dfa, s);
+  if (rc) {
+    ugpu_batch_free(r);
+    return rc;
+  }
+  r->first[ninputs] = r->count;
+  r->flags = all_one ? UGPU_BATCH_ONE_SCAN : 0u;
+  *out = r;
+  return UGPU_OK;
+}

@@ -621,6 +621,21 @@ int ugpu_tables_newline_host(const uint32_t* opc, uint32_t nop, int* nl)
   return UGPU_OK;
 }
 
+int ugpu_batch_plan_host(const uint32_t* opc, uint32_t nop, uint32_t pattern_flags, int* one_scan)
+{
+  if (!one_scan) return fail(UGPU_INVAL, "NULL argument");
+  *one_scan = 0;
+  ugpu_dfa_info info;
+  const int rc = ugpu_dfa_plan_host(opc, nop, pattern_flags, &info);
+  if (rc != UGPU_OK) return rc;
+  int nl = 1;
+  const int rn = ugpu_tables_newline_host(opc, nop, &nl);
+  if (rn != UGPU_OK) return rn;
+  // option N never reports an empty match at the end of the input: a per-input rule
+  *one_scan = !nl && !(pattern_flags & UGPU_PAT_EMPTY) ? 1 : 0;
+  return UGPU_OK;
+}
+
 int ugpu_tables_equivalent_host(const uint32_t* opc_a, uint32_t nop_a, const uint32_t* opc_b, uint32_t nop_b, int* eq)
 {
   if (!eq) return fail(UGPU_INVAL, "NULL argument");

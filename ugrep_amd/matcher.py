@@ -729,6 +729,88 @@ def host_newline(opc):
     return bool(nl.value)
 
 
+# --- batched FIND (ugpu_find_batch; replaces the per-file loop, src/ugrep.cpp:4261-4480) ---
+
+def host_batch_plan(opc, word=False, empty=False):
+    """ugpu_batch_plan_host: whether a batch on this table is served by one
+    scan of the packed inputs (no match can contain '\\n', no option N);
+    raises like Pattern() for unsupported tables."""
+    a, p = _as_u32(compile_regex(opc) if isinstance(opc, (str, bytes)) else opc)
+    one = ctypes.c_int()
+    check(lib.ugpu_batch_plan_host(p, len(a), (PAT_WORD if word else 0) | (PAT_EMPTY if empty else 0),
+                                   ctypes.byref(one)))
+    return bool(one.value)
+
+
+def split_matches(dptr, length, d_bounds, nseg, d_start, d_len, d_cap, cap1, n, d_first, d_digest, d_dcap,
+                  d_newlines, d_mlines, d_rel=0, d_line=0, stream=0):
+    """ugpu_split_matches over a 16-byte aligned device buffer, its sorted
+    device match list (d_len 0: zero lengths; d_cap 0: every accept index is
+    cap1) and nseg + 1 ascending device bounds: fills the per-segment device
+    arrays d_first (nseg + 1), d_digest, d_dcap, d_newlines, d_mlines (nseg) and,
+    when given, the per-record d_rel and d_line."""
+    v = ctypes.c_void_p
+    check(lib.ugpu_split_matches(v(dptr), length, v(d_bounds), nseg, v(d_start or None), v(d_len or None),
+                                 v(d_cap or None), cap1, n, v(d_first), v(d_digest or None), v(d_dcap or None),
+                                 v(d_newlines or None), v(d_mlines or None), v(d_rel or None), v(d_line or None),
+                                 v(stream)))
+
+
+class BatchResult:
+    """Per-input results of find_batch: input i owns the records
+    [first[i], first[i+1]); start is relative to its input, line is the 1-based
+    line within it; start, length, cap and line are None without offsets."""
+
+    def __init__(self, one_scan, count, first, digest, dcap, newlines, matching_lines, start=None, length=None,
+                 cap=None, line=None):
+        self.one_scan, self.count, self.first = one_scan, count, first
+        self.digest, self.dcap, self.newlines, self.matching_lines = digest, dcap, newlines, matching_lines
+        self.start, self.length, self.cap, self.line = start, length, cap, line
+
+    def __len__(self):
+        return len(self.digest)
+
+    def input(self, i):
+        """(FindResult, line slice) of input i."""
+        a, b = int(self.first[i]), int(self.first[i + 1])
+        if self.start is None:
+            return FindResult(b - a, int(self.digest[i]), int(self.dcap[i]), np.zeros(0, np.uint64),
+                              np.zeros(0, np.uint32), np.zeros(0, np.uint32)), None
+        return FindResult(b - a, int(self.digest[i]), int(self.dcap[i]), self.start[a:b], self.length[a:b],
+                          self.cap[a:b]), self.line[a:b]
+
+
+def find_batch(pattern, inputs, offsets=True):
+    """ugpu_find_batch: FIND over a sequence of host inputs (bytes, numpy or
+    host tensors) in one packed scan where the table allows it; every input's
+    results equal find_all and lines over that input alone."""
+    bufs = [_buffer_ptr(d) for d in inputs]
+    k = len(bufs)
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[b[0] if b[1] else None for b in bufs])
+    lens = np.array([b[1] for b in bufs], dtype=np.uint64)
+    res = ctypes.POINTER(_lib.BatchResult)()
+    check(lib.ugpu_find_batch(pattern.handle, ptrs, lens.ctypes.data_as(_lib.c_u64p), k,
+                              _lib.MODE_OFFSETS if offsets else _lib.MODE_COUNT, ctypes.byref(res)))
+    try:
+        r = res.contents
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dt)
+
+        out = BatchResult(bool(r.flags & _lib.BATCH_ONE_SCAN), r.count, arr(r.first, k + 1, np.uint64),
+                          arr(r.digest, k, np.uint64), arr(r.dcap, k, np.uint64), arr(r.newlines, k, np.uint64),
+                          arr(r.matching_lines, k, np.uint64))
+        if offsets:
+            out.start = arr(r.start, r.count, np.uint64)
+            out.length = arr(r.len, r.count, np.uint32)
+            out.cap = arr(r.cap, r.count, np.uint32)
+            out.line = arr(r.line, r.count, np.uint64)
+    finally:
+        lib.ugpu_batch_free(res)
+    del bufs
+    return out
+
+
 # --- ugrep --bool queries (grammar: src/cnf.hpp:227-237) ---
 #   and  -> or { space+ [ 'AND' space+ ] or }*
 #   or   -> not { ( '|'+ | 'OR' space+ ) not }*
