@@ -120,31 +120,25 @@ struct ugpu_dfa {
   std::atomic<int> batch_one{-1};
 };
 
+// what scanner_create set up for one kernel (rec == 0: not set up)
+struct KernelSetup {
+  int rec = 0;      // chain records per scan (blocks or waves)
+  size_t smem = 0;  // LDS bytes of a launch
+};
+
 struct ugpu_scanner {
   const ugpu_dfa* dfa = nullptr;
   int device = 0;
-  int max_rec = 0;       // chain records per scan (blocks or waves)
-  bool sparse = false;   // prefiltered wave-persistent kernel (sparse_kernel.hip)
-  bool xi = false;       // COUNT scans run xi_kernel (immediate tables); OFFSETS use the dense kernel
-  bool xg = false;       // COUNT scans run xg_kernel (gap tables); OFFSETS use the dense kernel
-  bool xc = false;       // COUNT and OFFSETS scans run xc_kernel (two-state and, U mode, code-point run tables)
-  bool xu_xi = false, xu_xg = false;  // U mode: the kernels a range goes to when it flags UGPU_FLAG_USLOW
-  bool xu = false;       // xc_kernel runs in U mode (code-point run tables)
-  bool pref_write = false;  // created for a records consumer (scanner_acquire)
-  bool last_xc = false;  // the last ugpu_scan ran xc_kernel
-  bool word = false;     // option W: every pass runs wfind_kernel (wfind.hip) (per scan when wfast)
-  bool wfast = false;    // option W on a \w+ table: non-W kernels when the scanned bytes are valid UTF-8
-  bool wu = false;       // ... and those scans run xc_kernel's U mode with the run-edge check (no isutf8 pass)
-  bool wforce = false;   // (the next scan of a wfast scanner runs wfind_kernel)
-  bool xu_exact = false; // U mode: scans run the exact kernel (after a range that flagged UGPU_FLAG_UMIX)
-  int word_rec = 0;      // chain records of a wfind scan
-  bool ngram = false;    // word scanners: the passes run ngram_kernel (plan_ngram) in wfind_kernel's place
-  bool wxc = false;      // option W on xc_kernel (dfa->xcw), wfind_kernel when it flags UGPU_FLAG_WSLOW
-  uint32_t bol0 = 1;     // dbuf[0] begins a line (ugpu_scanner_context; anchored tables)
-  size_t smem = 0;       // sparse / dense kernel
-  size_t xi_smem = 0;
-  int xi_rec = 0;        // chain records of an xi scan
-  bool last_xi = false;  // the last ugpu_scan ran xi_kernel
+  // the table's route (plan.hpp dfa_route) after this device's demotions, the
+  // kernels set up for it, and the step of the last scan
+  Route route;
+  KernelSetup ks[kKernels];
+  Step last_step;
+  // U mode: scans run the exact kernel (after a range that flagged
+  // UGPU_FLAG_UMIX) until the scanner goes back to its pool
+  bool xu_exact = false;
+  bool pref_write = false;  // created for a records consumer (scanner_acquire): which pool it returns to
+  uint32_t bol0 = 1;        // dbuf[0] begins a line (ugpu_scanner_context; anchored tables)
   const uint8_t* last_buf = nullptr;
   uint64_t last_args[5] = {0, 0, 0, 0, 0};  // lo, hi, read_end, at_eof, bias of the last scan
   BlockRec* d_recs = nullptr;
@@ -272,27 +266,9 @@ uint32_t fix_rounds_for(const ScanParams& P)
 
 int utf8_scan(const uint8_t* dbuf, uint64_t len, bool nul, uint64_t* pos, void* stream);
 
-// two-state tables run xc_kernel for COUNT scans (UGPU_XC=0: xi/xg/dense)
-bool dfa_xc(const ugpu_dfa* d)
-{
-  const char* env = std::getenv("UGPU_XC");
-  return d->t.xc && !d->t.filter && !d->lb && d->t.cap1 != 0 && (!d->d_wtab || d->xcw) && !(env && env[0] == '0');
-}
+bool on_xc(Step step) { return step.k == K_XC || step.k == K_XU; }
 
-// code-point run tables run xc_kernel's U mode for COUNT and OFFSETS scans
-// when they have no gap transducer: on C4 (\w+) xg_kernel measured 3.0 ms
-// against U mode's 3.17.  UGPU_XU=1 prefers U mode, UGPU_XU=0
-// never takes it.  Under option W only on \w+ (the W fast path).
-// code-point run tables take xc_kernel's U mode, also when they have a gap
-// transducer (C4 \w+: xu_kernel 2.30 ms, xg_kernel 2.94 ms; UGPU_XU=0 keeps
-// xg_kernel / the table's other kernel)
-bool dfa_xu(const ugpu_dfa* d)
-{
-  const char* env = std::getenv("UGPU_XU");
-  const bool off = env && env[0] == '0';
-  return d->d_xu && (!d->d_wtab || d->wplus) && !off;
-}
-
+// (the tables; scan_step adds what depends on the step: xu_tab, xu_w, xu_exact)
 void fill_tables(ScanParams& P, const ugpu_dfa* d)
 {
   P.trans = d->d_trans;
@@ -318,7 +294,6 @@ void fill_tables(ScanParams& P, const ugpu_dfa* d)
   P.xc_cls = d->d_cls + 256;
   // (option W on xc_kernel: 1 = X is the ASCII word bytes, 2 = a subset of them)
   P.xc_w = d->xcw ? (d->t.xc_w ? 1u : 2u) : 0u;
-  P.xu_tab = dfa_xu(d) ? d->d_xu : nullptr;
   P.xu_bm3 = d->d_xu ? reinterpret_cast<const uint32_t*>(d->d_xu + kXuTab) : nullptr;
   P.xu_null = d->t.xu_null;
   P.acap = d->amode ? d->d_acap : nullptr;
@@ -382,32 +357,44 @@ void geometry(ScanParams& P, const uint8_t* dbuf, uint64_t lo, uint64_t hi, uint
   P.max_rounds = fix_rounds_for(P);
 }
 
-void geometry_for(ScanParams& P, const ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi,
-                  uint64_t read_end, uint64_t& off, bool xi = false)
+// The scan kernels by number (plan.hpp Kernel): tile bytes, waves per block and
+// launcher (smem: the LDS bytes scanner_create worked out, where the kernel
+// takes them).  xi_kernel and xg_kernel have no WRITE pass (record_kernel).
+struct KernelDesc {
+  uint32_t (*unit)(uint32_t format);
+  uint32_t (*waves)(uint32_t format);
+  hipError_t (*launch)(const ScanParams& P, uint32_t format, bool write, size_t smem, hipStream_t st);
+};
+#define UGPU_U32(expr) [](uint32_t format) { (void)format; return (uint32_t)(expr); }
+#define UGPU_LAUNCH(expr) \
+  [](const ScanParams& P, uint32_t format, bool write, size_t smem, hipStream_t st) { \
+    (void)format, (void)write, (void)smem;                                             \
+    return expr;                                                                       \
+  }
+const KernelDesc kKernel[kKernels] = {
+    /* K_SPARSE */ {UGPU_U32(kWaveTile), UGPU_U32(kSpWaves), UGPU_LAUNCH(launch_sparse(P, write, smem, st))},
+    /* K_DENSE  */ {UGPU_U32(dense_unit(format)), UGPU_U32(dense_waves(format)),
+                    UGPU_LAUNCH(launch_dense(P, format, write, smem, st))},
+    /* K_XI     */ {UGPU_U32(xi_unit()), UGPU_U32(xi_waves()), UGPU_LAUNCH(launch_xi(P, smem, st))},
+    /* K_XG     */ {UGPU_U32(xg_unit()), UGPU_U32(xg_waves()), UGPU_LAUNCH(launch_xg(P, st))},
+    /* K_WFIND  */ {UGPU_U32(wfind_unit()), UGPU_U32(wfind_waves()), UGPU_LAUNCH(launch_wfind(P, format, write, st))},
+    /* K_XC     */ {UGPU_U32(xc_unit(false)), UGPU_U32(xc_waves()), UGPU_LAUNCH(launch_xc(P, write, st))},
+    /* K_XU     */ {UGPU_U32(xc_unit(true)), UGPU_U32(xc_waves()), UGPU_LAUNCH(launch_xc(P, write, st))},
+    /* K_NGRAM  */ {UGPU_U32(wfind_unit()), UGPU_U32(ngram_waves()), UGPU_LAUNCH(launch_ngram(P, format, write, st))},
+};
+#undef UGPU_U32
+#undef UGPU_LAUNCH
+
+void geometry_for(ScanParams& P, const ugpu_scanner* s, Kernel k, const uint8_t* dbuf, uint64_t lo, uint64_t hi,
+                  uint64_t read_end, uint64_t& off)
 {
-  if (s->word)
-    geometry(P, dbuf, lo, hi, read_end, s->word_rec, wfind_unit(), s->ngram ? ngram_waves() : wfind_waves(), off);
-  else if (xi && s->xc)
-    geometry(P, dbuf, lo, hi, read_end, s->xi_rec, xc_unit(s->xu), xc_waves(), off);
-  else if (xi && s->xg)
-    geometry(P, dbuf, lo, hi, read_end, s->xi_rec, xg_unit(), xg_waves(), off);
-  else if (xi)
-    geometry(P, dbuf, lo, hi, read_end, s->xi_rec, xi_unit(), xi_waves(), off);
-  else if (s->sparse)
-    geometry(P, dbuf, lo, hi, read_end, s->max_rec, kWaveTile, kSpWaves, off);
-  else
-    geometry(P, dbuf, lo, hi, read_end, s->max_rec, dense_unit(s->dfa->t.format), dense_waves(s->dfa->t.format), off);
+  const uint32_t format = s->dfa->t.format;
+  geometry(P, dbuf, lo, hi, read_end, s->ks[k].rec, kKernel[k].unit(format), kKernel[k].waves(format), off);
 }
 
-hipError_t launch_main(const ugpu_scanner* s, const ScanParams& P, bool write, hipStream_t st, bool xi = false)
+hipError_t launch_main(const ugpu_scanner* s, Kernel k, const ScanParams& P, bool write, hipStream_t st)
 {
-  if (s->word && s->ngram) return launch_ngram(P, s->dfa->t.format, write, st);
-  if (s->word) return launch_wfind(P, s->dfa->t.format, write, st);
-  if (xi && s->xc) return launch_xc(P, write, st);
-  if (xi && s->xg) return launch_xg(P, st);
-  if (xi) return launch_xi(P, s->xi_smem, st);
-  if (s->sparse) return launch_sparse(P, write, s->smem, st);
-  return launch_dense(P, s->dfa->t.format, write, s->smem, st);
+  return kKernel[k].launch(P, s->dfa->t.format, write, s->ks[k].smem, st);
 }
 
 bool is_device_ptr(const void* p)
@@ -733,9 +720,60 @@ int ugpu_scanner_create_ex(const ugpu_dfa* dfa, uint32_t flags, ugpu_scanner** o
 
 namespace {
 
-// prefer_write: code-point run tables take xc_kernel's U mode, which writes
-// its own records, also where xg_kernel (no record pass: OFFSETS rebuilt on
-// dense_kernel) counts a little faster -- the choice of a records consumer
+// a kernel's chain records: g, at most kMaxRec (UGPU_MAX_GRID overrides; testing)
+int clamp_grid(int g)
+{
+  if (g > kMaxRec) g = kMaxRec;
+  if (const char* env = std::getenv("UGPU_MAX_GRID")) {
+    const int v = std::atoi(env);
+    if (v >= 1 && v <= kMaxRec) g = v;
+  }
+  return g;
+}
+
+// the buffers and events every scanner has (sparse: and sparse_kernel's open and suspended walks)
+hipError_t scanner_alloc(ugpu_scanner* s, bool sparse)
+{
+  hipError_t e;
+  if ((e = hipMalloc(&s->d_recs, sizeof(BlockRec) * kMaxRec)) != hipSuccess ||
+      (e = hipMalloc(&s->d_entries, sizeof(uint64_t) * kMaxRec)) != hipSuccess ||
+      (e = hipMalloc(&s->d_obase, sizeof(uint64_t) * kMaxRec)) != hipSuccess ||
+      (e = hipMalloc(&s->d_fix, sizeof(uint64_t) * kMaxRec)) != hipSuccess)
+    return e;
+  if (sparse && ((e = hipMalloc(&s->d_open, sizeof(OpenRec) * kMaxRec)) != hipSuccess ||
+                 (e = hipMalloc(&s->d_susp, sizeof(uint32_t) * kMaxRec)) != hipSuccess ||
+                 (e = hipMalloc(&s->d_srec, sizeof(SuspRec) * kMaxRec)) != hipSuccess))
+    return e;
+  if ((e = hipMalloc(&s->d_tot, sizeof(DevTotals))) != hipSuccess ||
+      (e = hipMalloc(&s->d_flags, sizeof(uint32_t))) != hipSuccess ||
+      (e = hipHostMalloc(&s->h_tot, sizeof(DevTotals))) != hipSuccess ||
+      (e = hipHostMalloc(&s->h_flags, sizeof(uint32_t))) != hipSuccess ||
+      (e = hipEventCreate(&s->ev0)) != hipSuccess || (e = hipEventCreate(&s->ev1)) != hipSuccess)
+    return e;
+  return hipSuccess;
+}
+
+// The In bits of an xc_kernel COUNT pass over bytes [0, rend) of an aligned
+// buffer: one bit per byte up to the chunk after the readable end (the last
+// wave searches for the exit up to there).  Grows s->d_inbits; on failure the
+// scanner has none and OFFSETS runs the WRITE pass.
+void inbits_reserve(ugpu_scanner* s, uint64_t rend)
+{
+  const uint64_t need = ((((rend + 15) & ~uint64_t(15)) + 2048) >> 3) + 64;
+  if (need <= s->inbits_cap) return;
+  (void)hipFree(s->d_inbits);
+  s->d_inbits = nullptr;
+  s->inbits_cap = 0;
+  if (hipMalloc(&s->d_inbits, need + need / 8) == hipSuccess)
+    s->inbits_cap = need + need / 8;
+  else
+    (void)hipGetLastError();
+}
+
+// The table's route (plan.hpp dfa_route), minus what this device cannot run:
+// tables that do not fit in LDS are UGPU_UNSUPPORTED, and a kernel whose
+// occupancy query returns 0 is demoted (route_demote).  prefer_write: for a
+// records consumer (the In bits of ugpu_scan, and the pool it returns to).
 int scanner_create(const ugpu_dfa* dfa, ugpu_scanner** out, bool prefer_write)
 {
   if (!dfa || !out) return fail(UGPU_INVAL, "NULL argument");
@@ -762,171 +800,65 @@ int scanner_create(const ugpu_dfa* dfa, ugpu_scanner** out, bool prefer_write)
     }                                        \
   } while (0)
   HIP_TRY_S(hipGetDevice(&s->device));
-  // option W: prefiltered tables keep sparse_kernel (its candidate walks check
-  // the W rules); every other table runs wfind_kernel (tables through the caches)
-  // line anchors / option N: every scan runs the context walk on wfind_kernel
-  // wide tables: the exact walk on wfind_kernel, transitions from global memory
-  // context accepts (word boundaries, line anchors) on a prefiltered table:
-  // sparse_kernel's candidate walks run the context walk, the
-  // prefilter's candidates stay a superset; without a prefilter (or with
-  // UGPU_SPARSE=0) wfind_kernel's chain of context walks
-  // (option W: also loop-needle tables and DfaPlan::wsparse; UGPU_SPARSE=0:
-  // wfind_kernel, which applies the W rules)
-  const char* senv0 = std::getenv("UGPU_SPARSE");
-  const bool sp_off = senv0 && senv0[0] == '0';
-  const bool ctx_sparse = dfa->amode && dfa->t.filter && dfa->t.format == FMT_BYTE && !sp_off;
-  const bool w_sparse = (dfa->t.filter || dfa->lb || dfa->wsparse) && dfa->t.format == FMT_BYTE && !sp_off;
-  // lookahead tables: the lookahead walk (kWalkLook) on wfind_kernel
-  // n-gram tables (plan_ngram; UGPU_NG=0: off): ngram_kernel on wfind_kernel's
-  // records and passes, whatever kernel the table would take without it
-  const bool ngram = dfa->d_ngram && plan_ngram(dfa->t, dfa->plan);
-  if (ngram) {
-    s->ngram = true;
-    s->word = true;
-    s->word_rec = kMaxRec;
-    if (const char* env = std::getenv("UGPU_MAX_GRID")) {
-      int v = std::atoi(env);
-      if (v >= 1 && v <= kMaxRec) s->word_rec = v;
-    }
-    s->max_rec = s->word_rec;
-  } else if ((dfa->amode && !ctx_sparse) || dfa->t.format == FMT_WIDE || dfa->t.lookahead ||
-      (dfa->d_wtab && !dfa->amode && !w_sparse)) {
-    const uint32_t nacap = !dfa->amode ? dfa->t.states
-                           : dfa->t.ctx_word ? (uint32_t)dfa->t.acap_rows.size() : (uint32_t)dfa->t.acap.size();
-    const uint32_t nmap = dfa->amode && dfa->t.ctx_word ? dfa->t.states : 0u;
-    if (wfind_smem_bytes(dfa->ntrans_pad, dfa->t.states, dfa->nwtab, nacap, nmap) > 160 * 1024) {
+  const DfaTables& t = dfa->t;
+  Route r = dfa_route(t, dfa->plan);
+  const bool wredo = r.wmode == W_PLUS || r.wmode == W_XC;  // (set up the exact W kernel too)
+  for (Kernel k : {K_WFIND, K_NGRAM})
+    if (r.count.k == k || (wredo && r.wslow.k == k)) s->ks[k].rec = clamp_grid(kMaxRec);
+  if (s->ks[K_WFIND].rec) {
+    const uint32_t nacap = !dfa->amode ? t.states : t.ctx_word ? (uint32_t)t.acap_rows.size() : (uint32_t)t.acap.size();
+    const uint32_t nmap = dfa->amode && t.ctx_word ? t.states : 0u;
+    if (wfind_smem_bytes(dfa->ntrans_pad, t.states, dfa->nwtab, nacap, nmap) > 160 * 1024) {
       delete s;
       return fail(UGPU_UNSUPPORTED, "tables do not fit in LDS");
     }
-    s->word = true;
-    s->word_rec = kMaxRec;
-    if (const char* env = std::getenv("UGPU_MAX_GRID")) {
-      int v = std::atoi(env);
-      if (v >= 1 && v <= kMaxRec) s->word_rec = v;
+  }
+  const bool sparse = r.count.k == K_SPARSE;
+  if (r.count.k != K_WFIND && r.count.k != K_NGRAM) {
+    // sparse_kernel, or dense_kernel: the records of xi / xg scans and the
+    // geometry of ugpu_chain_fix also where COUNT scans run another kernel
+    const Kernel base = sparse ? K_SPARSE : K_DENSE;
+    size_t& smem = s->ks[base].smem;
+    smem = sparse ? sparse_smem_bytes(dfa->ntrans_pad, t.states, acap_lds_n(dfa))
+                  : dense_smem_bytes(t.format, dfa->ntrans_pad, t.states);
+    if (smem > 160 * 1024) {
+      delete s;
+      return fail(UGPU_UNSUPPORTED, "tables do not fit in LDS");
     }
-    s->max_rec = s->word_rec;
-  }
-  if (s->word && dfa->wplus) {
-    // \w+ under option W: set up the non-W kernels too; ugpu_scan picks per scan
-    s->word = false;
-    s->wfast = true;
-  } else if (s->word && dfa->xcw) {
-    s->word = false;  // xc_kernel with the W rules; wfind_kernel when it flags non-ASCII bytes
-    s->wxc = true;
-  }
-  if (s->word) {
-    HIP_TRY_S(hipMalloc(&s->d_recs, sizeof(BlockRec) * kMaxRec));
-    HIP_TRY_S(hipMalloc(&s->d_entries, sizeof(uint64_t) * kMaxRec));
-    HIP_TRY_S(hipMalloc(&s->d_obase, sizeof(uint64_t) * kMaxRec));
-    HIP_TRY_S(hipMalloc(&s->d_fix, sizeof(uint64_t) * kMaxRec));
-    HIP_TRY_S(hipMalloc(&s->d_tot, sizeof(DevTotals)));
-    HIP_TRY_S(hipMalloc(&s->d_flags, sizeof(uint32_t)));
-    HIP_TRY_S(hipHostMalloc(&s->h_tot, sizeof(DevTotals)));
-    HIP_TRY_S(hipHostMalloc(&s->h_flags, sizeof(uint32_t)));
-    HIP_TRY_S(hipEventCreate(&s->ev0));
-    HIP_TRY_S(hipEventCreate(&s->ev1));
-    *out = s;
-    return UGPU_OK;
-  }
-  // (UGPU_SPARSE=0: prefiltered tables take the dense-pattern kernels; testing)
-  const char* senv = std::getenv("UGPU_SPARSE");
-  s->sparse = (dfa->t.filter || dfa->lb || dfa->wsparse) && dfa->t.format == FMT_BYTE && !(senv && senv[0] == '0');
-  s->smem = s->sparse ? sparse_smem_bytes(dfa->ntrans_pad, dfa->t.states, acap_lds_n(dfa))
-                      : dense_smem_bytes(dfa->t.format, dfa->ntrans_pad, dfa->t.states);
-  if (s->smem > 160 * 1024) {
-    delete s;
-    return fail(UGPU_UNSUPPORTED, "tables do not fit in LDS");
-  }
-  int per_cu = 0;
-  if (s->sparse) {
-    ScanParams probe{};
-    HIP_TRY_S(sparse_occupancy(probe, s->smem, &per_cu));
-  } else {
-    HIP_TRY_S(dense_occupancy(dfa->t.format, dfa->t.cap1 != 0, dfa->d_xtrans != nullptr, s->smem, &per_cu));
-  }
-  hipDeviceProp_t prop;
-  HIP_TRY_S(hipGetDeviceProperties(&prop, s->device));
-  if (per_cu < 1) per_cu = 1;
-  int g = prop.multiProcessorCount * per_cu * (s->sparse ? kSpWaves : dense_waves(dfa->t.format));
-  if (g > kMaxRec) g = kMaxRec;
-  s->max_rec = g;
-  if (const char* env = std::getenv("UGPU_MAX_GRID")) {
-    int v = std::atoi(env);
-    if (v >= 1 && v <= kMaxRec) s->max_rec = v;
-  }
-  // immediate tables: COUNT scans on xi_kernel (UGPU_XI=0 keeps the dense kernel);
-  // gap tables: xg_kernel (UGPU_XG=0 keeps the dense kernel)
-  const char* xenv = std::getenv("UGPU_XI");
-  const char* genv = std::getenv("UGPU_XG");
-  if (!s->sparse && !(dfa->d_xid && !(xenv && xenv[0] == '0')) && dfa->d_xg && !(genv && genv[0] == '0')) {
-    int gpc = 0;
-    HIP_TRY_S(xg_occupancy((uint32_t)((dfa->t.xg2.size() + 7) & ~size_t(7)), &gpc));
-    if (gpc >= 1) {
-      s->xg = true;
-      int gg = prop.multiProcessorCount * gpc * (int)xg_waves();
-      s->xi_rec = gg > kMaxRec ? kMaxRec : gg;
-      if (const char* env = std::getenv("UGPU_MAX_GRID")) {
-        int v = std::atoi(env);
-        if (v >= 1 && v <= kMaxRec) s->xi_rec = v;
+    int per_cu = 0;
+    if (sparse) {
+      ScanParams probe{};
+      HIP_TRY_S(sparse_occupancy(probe, smem, &per_cu));
+    } else {
+      HIP_TRY_S(dense_occupancy(t.format, t.cap1 != 0, dfa->d_xtrans != nullptr, smem, &per_cu));
+    }
+    hipDeviceProp_t prop;
+    HIP_TRY_S(hipGetDeviceProperties(&prop, s->device));
+    if (per_cu < 1) per_cu = 1;
+    const int cus = prop.multiProcessorCount;
+    s->ks[base].rec = clamp_grid(cus * per_cu * (int)kKernel[base].waves(t.format));
+    // the table's kernel behind xc_kernel, then xc_kernel
+    for (int pass = 0; pass < 2 && !sparse; ++pass) {
+      const Kernel k = pass == 0 ? r.uslow.k : r.count.k;
+      if (k == K_DENSE || s->ks[k].rec) continue;
+      int per = 0;
+      if (k == K_XG) {
+        HIP_TRY_S(xg_occupancy((uint32_t)((t.xg2.size() + 7) & ~size_t(7)), &per));
+      } else if (k == K_XI) {
+        s->ks[k].smem = (size_t)t.xid_rows * 256;
+        HIP_TRY_S(xi_occupancy(s->ks[k].smem, &per));
+      } else {
+        HIP_TRY_S(xc_occupancy(k == K_XU, &per));
       }
+      if (per >= 1)
+        s->ks[k].rec = clamp_grid(cus * per * (int)kKernel[k].waves(t.format));
+      else
+        r = route_demote(r, k);
     }
   }
-  if (!s->sparse && dfa->d_xid && !(xenv && xenv[0] == '0')) {
-    s->xi_smem = (size_t)dfa->t.xid_rows * 256;
-    int xpc = 0;
-    HIP_TRY_S(xi_occupancy(s->xi_smem, &xpc));
-    if (xpc >= 1) {
-      s->xi = true;
-      int xg = prop.multiProcessorCount * xpc * (int)xi_waves();
-      s->xi_rec = xg > kMaxRec ? kMaxRec : xg;
-      if (const char* env = std::getenv("UGPU_MAX_GRID")) {
-        int v = std::atoi(env);
-        if (v >= 1 && v <= kMaxRec) s->xi_rec = v;
-      }
-    }
-  }
-  // two-state tables: COUNT scans on xc_kernel, ahead of xi/xg (UGPU_XC=0
-  // keeps those)
-  const char* uenv = std::getenv("UGPU_XU");
-  // option W on \w+ (wfast): U mode checks the run edges itself, one pass
-  // instead of isutf8 + xg_kernel (UGPU_XUW=0 keeps those)
-  const char* wuenv = std::getenv("UGPU_XUW");
-  const bool wu = s->wfast && dfa->d_xu && !(wuenv && wuenv[0] == '0') && !(uenv && uenv[0] == '0');
-  const bool xu = dfa_xu(dfa) || wu ||
-                  (prefer_write && dfa->d_xu && (!dfa->d_wtab || dfa->wplus) && !(uenv && uenv[0] == '0'));
-  if (!s->sparse && (dfa_xc(dfa) || xu)) {
-    int cpc = 0;
-    HIP_TRY_S(xc_occupancy(xu, &cpc));
-    if (cpc >= 1) {
-      s->xc = true;
-      s->xu = xu;
-      s->wu = wu;
-      s->xu_xi = s->xi;
-      s->xu_xg = s->xg;
-      s->xi = s->xg = false;
-      const int cg = prop.multiProcessorCount * cpc * (int)xc_waves();
-      s->xi_rec = cg > kMaxRec ? kMaxRec : cg;
-      if (const char* env = std::getenv("UGPU_MAX_GRID")) {
-        int v = std::atoi(env);
-        if (v >= 1 && v <= kMaxRec) s->xi_rec = v;
-      }
-    }
-  }
-  HIP_TRY_S(hipMalloc(&s->d_recs, sizeof(BlockRec) * kMaxRec));
-  HIP_TRY_S(hipMalloc(&s->d_entries, sizeof(uint64_t) * kMaxRec));
-  HIP_TRY_S(hipMalloc(&s->d_obase, sizeof(uint64_t) * kMaxRec));
-  HIP_TRY_S(hipMalloc(&s->d_fix, sizeof(uint64_t) * kMaxRec));
-  if (s->sparse) {
-    HIP_TRY_S(hipMalloc(&s->d_open, sizeof(OpenRec) * kMaxRec));
-    HIP_TRY_S(hipMalloc(&s->d_susp, sizeof(uint32_t) * kMaxRec));
-    HIP_TRY_S(hipMalloc(&s->d_srec, sizeof(SuspRec) * kMaxRec));
-  }
-  HIP_TRY_S(hipMalloc(&s->d_tot, sizeof(DevTotals)));
-  HIP_TRY_S(hipMalloc(&s->d_flags, sizeof(uint32_t)));
-  HIP_TRY_S(hipHostMalloc(&s->h_tot, sizeof(DevTotals)));
-  HIP_TRY_S(hipHostMalloc(&s->h_flags, sizeof(uint32_t)));
-  HIP_TRY_S(hipEventCreate(&s->ev0));
-  HIP_TRY_S(hipEventCreate(&s->ev1));
+  s->route = r;
+  s->last_step = r.count;
+  HIP_TRY_S(scanner_alloc(s, sparse));
   *out = s;
   return UGPU_OK;
 #undef HIP_TRY_S
@@ -960,42 +892,32 @@ int ugpu_scanner_destroy(ugpu_scanner* s)
   return UGPU_OK;
 }
 
-int ugpu_scan(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi, uint64_t read_end, int at_eof,
+namespace {
+
+const char* step_mode(Step step)
+{
+  static const char* const u[4] = {"", " exact", " edge", " edge exact"};
+  return step.k == K_XU ? u[step.u & 3] : step.w ? " w" : "";
+}
+
+// One step of a scan of dbuf[lo, hi): the step's kernel (COUNT) and the
+// stitch, asynchronously on `stream`; the scanner remembers the step and the
+// range (ugpu_scan_totals redoes it on another step, ugpu_scan_offsets writes
+// its records)
+int scan_step(ugpu_scanner* s, Step step, const uint8_t* dbuf, uint64_t lo, uint64_t hi, uint64_t read_end, int at_eof,
               uint64_t bias, void* stream)
 {
-  if (!s || !dbuf) return fail(UGPU_INVAL, "NULL argument");
-  if (lo > hi || hi > read_end) return fail(UGPU_INVAL, "need lo <= hi <= read_end");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (s->wxc) s->word = false;
-  if (s->wfast) {
-    // option W on \w+: matches are maximal runs of Word code points, so on valid
-    // UTF-8 at_wb/at_we hold at every match edge (DESIGN 3.8) -- provided the
-    // chain enters at the buffer start or after an ASCII non-word byte
-    bool fast = !s->wforce;
-    if (fast && lo > 0) {
-      uint8_t b = 0;
-      HIP_TRY(hipMemcpyAsync(&b, dbuf + lo - 1, 1, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      fast = b == '\n' || (b < 0x80 && b != '_' && !((b | 0x20u) - 'a' < 26u) && !(b - '0' < 10u));
-    }
-    // isutf8 over [lo, read_end) first (run beside the scan on a second stream
-    // it gained nothing: the two kernels slowed each other down)
-    if (fast && read_end > lo && !s->wu) {
-      uint64_t bad = ~0ull;
-      const int rc = utf8_scan(dbuf + lo, read_end - lo, false, &bad, stream);
-      if (rc) return rc;
-      fast = bad == ~0ull;
-    }
-    s->word = !fast;
-  }
+  if (!s->ks[step.k].rec) return fail(UGPU_INVAL, "scan step on a kernel the scanner did not set up");
+  const bool sparse = step.k == K_SPARSE;
   ScanParams P{};
   fill_tables(P, s->dfa);
-  P.xu_tab = s->xu ? s->dfa->d_xu : nullptr;  // (the scanner's U mode choice)
-  P.xu_w = s->wu && !s->word ? 1u : 0u;
-  P.xu_exact = s->xu_exact ? 1u : 0u;
+  P.xu_tab = step.k == K_XU ? s->dfa->d_xu : nullptr;
+  P.xu_w = step.u & U_EDGE ? 1u : 0u;
+  P.xu_exact = step.u & U_EXACT ? 1u : 0u;
   P.bol0 = s->bol0;
-  if (s->wfast && !s->word) P.wtab = nullptr, P.nwtab = 0;  // the non-W kernels, stitches and forest
-  geometry_for(P, s, dbuf, lo, hi, read_end, s->off, s->xi || s->xg || s->xc);
+  if (s->route.wmode == W_PLUS && !step.w) P.wtab = nullptr, P.nwtab = 0;  // the non-W kernels, stitches and forest
+  geometry_for(P, s, step.k, dbuf, lo, hi, read_end, s->off);
   P.delta = (int64_t)bias - (int64_t)s->off;
   P.at_eof = at_eof ? 1u : 0u;
   if (const char* ab = std::getenv("UGPU_ABLATE")) P.ablate = (uint32_t)std::atoi(ab);
@@ -1008,14 +930,14 @@ int ugpu_scan(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi, ui
   // by fix_kernel): a long match costs each wave its own bytes only
   // (UGPU_TRUNC=0: walks run to the readable end)
   static const bool trunc = env_u64("UGPU_TRUNC", 1) != 0;
-  P.open = s->sparse && !P.wtab && !P.acap && trunc ? s->d_open : nullptr;
+  P.open = sparse && !P.wtab && !P.acap && trunc ? s->d_open : nullptr;
   // walks longer than their window: the wave suspends, a resume launch of
   // the kernel completes it (coop_walk); option W and the context walks keep
   // their per-lane walks
-  P.susp = s->sparse && !P.wtab && !P.acap ? s->d_susp : nullptr;
+  P.susp = sparse && !P.wtab && !P.acap ? s->d_susp : nullptr;
   P.srec = P.susp ? s->d_srec : nullptr;
   s->staged_last = false;
-  if (s->sparse && (s->stage || s->stage_once)) {
+  if (sparse && (s->stage || s->stage_once)) {
     if (!s->d_st_n) {
       // all four or none (a partial failure frees what it got)
       const size_t n = (size_t)kMaxRec * kStagePer;
@@ -1050,34 +972,21 @@ int ugpu_scan(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi, ui
   // (default on, round 4: with the expansion's coalesced length stores and
   // 12-byte records, C4 OFFSETS 6.4 ms against 8.1 ms for the WRITE pass, C3
   // 9.8 against 11.7 ms, profiles/r04_offsets_ab.txt; UGPU_XC_BITMAP=0 restores it)
-  if (s->pref_write && s->xc && !s->word && !P.xc_w && !P.xu_w && env_u64("UGPU_XC_BITMAP", 1) != 0) {
-    // one bit per byte up to the chunk after the readable end (the last wave
-    // searches for the exit up to there)
-    const uint64_t need = ((((P.rend + 15) & ~uint64_t(15)) + 2048) >> 3) + 64;
-    if (need > s->inbits_cap) {
-      (void)hipFree(s->d_inbits);
-      s->d_inbits = nullptr;
-      s->inbits_cap = 0;
-      if (hipMalloc(&s->d_inbits, need + need / 8) == hipSuccess)
-        s->inbits_cap = need + need / 8;
-      else
-        (void)hipGetLastError();  // (no bitmap: OFFSETS runs the WRITE pass)
-    }
+  if (s->pref_write && on_xc(step) && !P.xc_w && !P.xu_w && env_u64("UGPU_XC_BITMAP", 1) != 0) {
+    inbits_reserve(s, P.rend);
     if (s->d_inbits) P.inbits = s->d_inbits;
   }
-  UGPU_TRACE("scan lo %llu hi %llu rend %llu eof %d grid %u xi %d xg %d sparse %d word %d\n", (unsigned long long)P.lo,
-             (unsigned long long)P.hi, (unsigned long long)P.rend, at_eof, P.grid, (int)s->xi, (int)s->xg,
-             (int)s->sparse, (int)s->word);
+  UGPU_TRACE("scan lo %llu hi %llu rend %llu eof %d grid %u kernel %d%s\n", (unsigned long long)P.lo,
+             (unsigned long long)P.hi, (unsigned long long)P.rend, at_eof, P.grid, (int)step.k, step_mode(step));
   HIP_TRY(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t), st));
   HIP_TRY(hipEventRecord(s->ev0, st));
-  HIP_TRY(launch_main(s, P, false, st, s->xi || s->xg || s->xc));
+  HIP_TRY(launch_main(s, step.k, P, false, st));
   HIP_TRY(hipEventRecord(s->ev1, st));
   HIP_TRY(launch_fix(P, s->dfa->t.format, st));
   HIP_TRY(hipMemcpyAsync(s->h_tot, s->d_tot, sizeof(DevTotals), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(s->h_flags, s->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   s->last = P;
-  s->last_xi = !s->word && (s->xi || s->xg || s->xc);
-  s->last_xc = !s->word && s->xc;
+  s->last_step = step;
   s->last_buf = dbuf;
   s->last_args[0] = lo;
   s->last_args[1] = hi;
@@ -1088,6 +997,71 @@ int ugpu_scan(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi, ui
   s->have_scan = true;
   s->forest = false;
   return UGPU_OK;
+}
+
+// The step that redoes a range whose scan on `last` ended with `flags`, if any
+// (in this order of precedence; each leads to a step no later rule sends back)
+bool fallback(const Route& r, Step last, uint32_t flags, Step* next)
+{
+  if (last.k == K_XU && !(last.u & U_EXACT) && (flags & UGPU_FLAG_UMIX)) {
+    // U mode's fast kernel met an XU_MIX or XU_SLOW lead: the exact U kernel
+    // (which flags UGPU_FLAG_USLOW for 4-byte tokens)
+    *next = last;
+    next->u |= U_EXACT;
+  } else if ((last.u & U_EDGE) && (flags & (UGPU_FLAG_WSLOW | UGPU_FLAG_USLOW))) {
+    // option W on U mode met a stray continuation byte right after a token
+    // byte (at_wb may decode a word character there, xc_kernel.hip umask) or a
+    // 4-byte token: the exact W kernel
+    *next = r.wslow;
+  } else if (r.wmode == W_XC && last != r.wslow && (flags & UGPU_FLAG_WSLOW)) {
+    // option W on xc_kernel met bytes >= 0x80 (their at_wb/at_we need the
+    // UTF-8 decode): the exact W kernel
+    *next = r.wslow;
+  } else if (on_xc(last) && (flags & UGPU_FLAG_USLOW)) {
+    // U mode met a lead byte of a 4-byte token: the table's kernel behind xc_kernel
+    *next = r.uslow;
+    next->w = last.w;
+  } else {
+    return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+int ugpu_scan(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi, uint64_t read_end, int at_eof,
+              uint64_t bias, void* stream)
+{
+  if (!s || !dbuf) return fail(UGPU_INVAL, "NULL argument");
+  if (lo > hi || hi > read_end) return fail(UGPU_INVAL, "need lo <= hi <= read_end");
+  Step step = s->route.count;
+  if (s->route.wmode == W_PLUS) {
+    // option W on \w+: matches are maximal runs of Word code points, so on valid
+    // UTF-8 at_wb/at_we hold at every match edge (DESIGN 3.8) -- provided the
+    // chain enters at the buffer start or after an ASCII non-word byte
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    bool fast = true;
+    if (lo > 0) {
+      uint8_t b = 0;
+      HIP_TRY(hipMemcpyAsync(&b, dbuf + lo - 1, 1, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      fast = b == '\n' || (b < 0x80 && b != '_' && !((b | 0x20u) - 'a' < 26u) && !(b - '0' < 10u));
+    }
+    // isutf8 over [lo, read_end) first (run beside the scan on a second stream
+    // it gained nothing: the two kernels slowed each other down); U mode's
+    // run-edge check needs none
+    if (fast && read_end > lo && !(step.u & U_EDGE)) {
+      uint64_t bad = ~0ull;
+      const int rc = utf8_scan(dbuf + lo, read_end - lo, false, &bad, stream);
+      if (rc) return rc;
+      fast = bad == ~0ull;
+    }
+    if (!fast) step = s->route.wslow;
+  }
+  // (inputs with XU_MIX / XU_SLOW leads usually have many: the exact U kernel
+  // once one was met, until the scanner goes back to its pool)
+  if (step.k == K_XU && s->xu_exact) step.u |= U_EXACT;
+  return scan_step(s, step, dbuf, lo, hi, read_end, at_eof, bias, stream);
 }
 
 int ugpu_scanner_context(ugpu_scanner* s, int bol0)
@@ -1102,49 +1076,10 @@ int ugpu_scan_totals(ugpu_scanner* s, ugpu_totals* out)
   if (!s || !out) return fail(UGPU_INVAL, "NULL argument");
   if (!s->have_scan) return fail(UGPU_INVAL, "no scan issued");
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (s->last_xc && s->xu && (*s->h_flags & UGPU_FLAG_UMIX)) {
-    // U mode's fast kernel met an XU_MIX or XU_SLOW lead: redo the range with
-    // the exact U kernel (which flags UGPU_FLAG_USLOW for 4-byte tokens)
-    // (and keeps it for the scanner's later scans: inputs with such leads
-    // usually have many)
-    s->xu_exact = true;
-    const int rc = ugpu_scan(s, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2],
+  for (Step next; fallback(s->route, s->last_step, *s->h_flags, &next);) {
+    if (next.u & U_EXACT) s->xu_exact = true;
+    const int rc = scan_step(s, next, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2],
                              (int)s->last_args[3], s->last_args[4], s->stream);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  if (s->wu && !s->word && (*s->h_flags & (UGPU_FLAG_WSLOW | UGPU_FLAG_USLOW))) {
-    // option W on U mode met a stray continuation byte right after a token
-    // byte (at_wb may decode a word character there, xc_kernel.hip umask) or a
-    // 4-byte token: redo the range with wfind_kernel
-    s->wforce = true;
-    const int rc = ugpu_scan(s, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2],
-                             (int)s->last_args[3], s->last_args[4], s->stream);
-    s->wforce = false;
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  if (s->wxc && !s->word && (*s->h_flags & UGPU_FLAG_WSLOW)) {
-    // option W met bytes >= 0x80 (their at_wb/at_we need the UTF-8 decode):
-    // redo the range with wfind_kernel
-    s->wxc = false;
-    s->word = true;
-    const int rc = ugpu_scan(s, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2],
-                             (int)s->last_args[3], s->last_args[4], s->stream);
-    s->wxc = true;
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  if (s->last_xc && (*s->h_flags & UGPU_FLAG_USLOW)) {
-    // U mode met a lead byte of a 4-byte token: redo the range with the
-    // table's next kernel (xg / xi / dense)
-    s->xc = false;
-    s->xi = s->xu_xi;
-    s->xg = s->xu_xg;
-    const int rc = ugpu_scan(s, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2],
-                             (int)s->last_args[3], s->last_args[4], s->stream);
-    s->xc = true;
-    s->xi = s->xg = false;
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
@@ -1165,7 +1100,8 @@ int ugpu_scan_totals(ugpu_scanner* s, ugpu_totals* out)
   out->entry = t.entry - s->off;
   out->exit = t.exit - s->off;
   out->flags = (*s->h_flags & ~(UGPU_FLAG_WSLOW | UGPU_FLAG_OPEN)) | (s->forest ? UGPU_TOT_FOREST : 0u) |
-               ((s->wfast || s->wxc) && !s->word ? UGPU_TOT_WFAST : 0u);
+               ((s->route.wmode == W_PLUS || s->route.wmode == W_XC) && s->last_step != s->route.wslow ? UGPU_TOT_WFAST
+                                                                                                      : 0u);
   out->fix_rounds = t.rounds;
   if (out->flags & UGPU_FLAG_HALO) return fail(UGPU_HALO, "a match walked past the readable end of the shard");
   if (out->flags & UGPU_FLAG_BUDGET) return fail(UGPU_UNSUPPORTED, kBudgetMsg);
@@ -1197,7 +1133,8 @@ int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint3
   HIP_TRY(hipStreamSynchronize(s->stream));
   ScanParams P = s->last;
   bool forest = s->forest || (*s->h_flags & UGPU_FLAG_BUDGET);
-  if (s->last_xc && !forest) {
+  const Kernel rk = record_kernel(s->last_step.k);
+  if (on_xc(s->last_step) && !forest) {
     // xc_kernel writes its own records (starts, then lengths from the ends),
     // at the output bases of the COUNT pass's exact records
     P.out_base = s->d_obase;
@@ -1217,16 +1154,15 @@ int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint3
     if (*s->h_flags & UGPU_FLAG_HALO) return fail(UGPU_HALO, "a match walked past the readable end of the shard");
     return UGPU_OK;
   }
-  if (s->last_xi && s->wxc) s->word = true;  // (not reached: xc writes its own W records)
-  if (s->last_xi && !forest) {
-    // xi_kernel has no record-writing pass: redo the chain records with the
-    // dense kernel's geometry (COUNT + fix), then its WRITE pass
+  if (rk != s->last_step.k && !forest) {
+    // xi_kernel and xg_kernel have no record-writing pass: redo the chain
+    // records with the dense kernel's geometry (COUNT + fix), then its WRITE pass
     P = ScanParams{};
     fill_tables(P, s->dfa);
     P.bol0 = s->bol0;
-    if (s->wfast) P.wtab = nullptr, P.nwtab = 0;  // (only a non-W scan gets here)
+    if (s->route.wmode == W_PLUS) P.wtab = nullptr, P.nwtab = 0;  // (only a non-W scan gets here)
     uint64_t off = 0;
-    geometry_for(P, s, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2], off, false);
+    geometry_for(P, s, rk, s->last_buf, s->last_args[0], s->last_args[1], s->last_args[2], off);
     P.delta = (int64_t)s->last_args[4] - (int64_t)off;
     P.at_eof = (uint32_t)s->last_args[3];
     P.recs = s->d_recs;
@@ -1234,8 +1170,9 @@ int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint3
     P.totals = s->d_tot;
     P.entries_out = s->d_entries;
     P.out_base_out = s->d_obase;
+    UGPU_TRACE("offsets recount kernel %d\n", (int)rk);
     HIP_TRY(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t), st));
-    HIP_TRY(launch_main(s, P, false, st));
+    HIP_TRY(launch_main(s, rk, P, false, st));
     HIP_TRY(launch_fix(P, s->dfa->t.format, st));
     HIP_TRY(hipMemcpyAsync(s->h_flags, s->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1249,7 +1186,7 @@ int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint3
   P.out_capacity = capacity;
   UGPU_TRACE("offsets forest %d capacity %llu staged %d\n", (int)forest, (unsigned long long)capacity,
              (int)s->staged_last);
-  if (!forest && s->staged_last && !s->last_xi) {
+  if (!forest && s->staged_last && rk == s->last_step.k) {
     // single pass: copy the staged records of waves whose speculative chain was
     // the true one; a WRITE pass (skipping the copied waves) covers the rest
     HIP_TRY(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t), st));
@@ -1264,7 +1201,8 @@ int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint3
   }
   if (!forest) {
     HIP_TRY(hipMemsetAsync(s->d_flags, 0, sizeof(uint32_t), st));
-    HIP_TRY(launch_main(s, P, true, st));
+    UGPU_TRACE("offsets write kernel %d\n", (int)rk);
+    HIP_TRY(launch_main(s, rk, P, true, st));
     HIP_TRY(hipMemcpyAsync(s->h_flags, s->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     forest = (*s->h_flags & UGPU_FLAG_BUDGET) != 0;  // a lane stitch ran past its round budget
@@ -1288,8 +1226,10 @@ int ugpu_chain_fix(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t h
   ScanParams P{};
   fill_tables(P, s->dfa);
   P.bol0 = s->bol0;
+  // (the geometry of the last scan's record kernel; dense_kernel's where that is xc_kernel)
+  const Kernel k = on_xc(s->last_step) ? K_DENSE : record_kernel(s->last_step.k);
   uint64_t off = 0;
-  geometry_for(P, s, dbuf, lo, hi, read_end, off);
+  geometry_for(P, s, k, dbuf, lo, hi, read_end, off);
   P.delta = (int64_t)bias - (int64_t)off;
   P.at_eof = at_eof ? 1u : 0u;
   P.totals = s->d_tot;
@@ -3004,19 +2944,8 @@ int ugpu_stream_reserve(const ugpu_dfa* dfa, int n, uint64_t feed_bytes)
     rc = scanner_acquire(dfa, &s, true);
     if (rc) break;
     scs.push_back(s);
-    if (s->xc && !s->word && env_u64("UGPU_XC_BITMAP", 1) != 0) {
-      // (the In bits of a COUNT pass over a whole buffer, as ugpu_scan sizes them)
-      const uint64_t nb = ((((c + 16 + 15) & ~uint64_t(15)) + 2048) >> 3) + 64;
-      if (nb > s->inbits_cap) {
-        (void)hipFree(s->d_inbits);
-        s->d_inbits = nullptr;
-        s->inbits_cap = 0;
-        if (hipMalloc(&s->d_inbits, nb + nb / 8) == hipSuccess)
-          s->inbits_cap = nb + nb / 8;
-        else
-          (void)hipGetLastError();
-      }
-    }
+    // (the In bits of a COUNT pass over a whole buffer, as ugpu_scan sizes them)
+    if (on_xc(s->route.count) && env_u64("UGPU_XC_BITMAP", 1) != 0) inbits_reserve(s, c + 16);
     FindWs* w = find_ws_acquire(dev);
     if (!w) {
       rc = fail(UGPU_NOMEM, "stream workspace");

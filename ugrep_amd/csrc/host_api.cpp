@@ -303,40 +303,54 @@ bool plan_filter2(const DfaTables& t, const DfaPlan& p)
 }
 
 namespace {
-// the kernel of a COUNT scan without the n-gram kernel
-uint32_t base_kernel(const DfaTables& t, const DfaPlan& p)
+bool knob_off(const char* name)
 {
-  const char* xenv = std::getenv("UGPU_XI");
-  const char* genv = std::getenv("UGPU_XG");
-  const char* cenv = std::getenv("UGPU_XC");
-  const char* uenv = std::getenv("UGPU_XU");
-  const char* senv = std::getenv("UGPU_SPARSE");
-  const bool byte_filter = (t.filter || p.lb || p.wsparse) && t.format == FMT_BYTE && !(senv && senv[0] == '0');
-  // (dfa_xc and dfa_xu, from the plan instead of the uploaded tables)
-  const bool xc = t.xc && !t.filter && !p.lb && t.cap1 != 0 && (!p.wtab || p.xcw) && !(cenv && cenv[0] == '0');
-  const bool xu = p.xu && (!p.wtab || p.wplus) && !(uenv && uenv[0] == '0');
-  // (context accepts on a prefiltered table: sparse_kernel's context walks)
-  return (p.amode && !byte_filter) || t.format == FMT_WIDE || t.lookahead ||
-                 (p.wtab && !p.wplus && !p.xcw && !byte_filter)
-             ? 4u
-         : byte_filter                                   ? 0u
-         : xc                                            ? 5u
-         : xu                                            ? 6u
-         : (p.xid && !(xenv && xenv[0] == '0'))          ? 2u
-         : (p.xg && !(genv && genv[0] == '0'))           ? 3u
-                                                         : 1u;
+  const char* v = std::getenv(name);
+  return v && v[0] == '0';
 }
 }  // namespace
 
-bool plan_ngram(const DfaTables& t, const DfaPlan& p)
+Route dfa_route(const DfaTables& t, const DfaPlan& p)
 {
-  const char* env = std::getenv("UGPU_NG");
-  if (env && env[0] == '0') return false;
-  if (t.ng_n < 2 || t.format == FMT_BYTE || p.amode || p.nul || t.lookahead || t.redo || t.start >= t.accb) return false;
-  if (t.ng_density > kNgramBound) return false;
-  const uint32_t k = base_kernel(t, p);
-  return k == 1u || k == 4u;
+  Route r;
+  r.wmode = p.wplus ? W_PLUS : p.xcw ? W_XC : p.wtab ? W_EXACT : W_NONE;
+  // prefiltered byte tables (option W: also loop-needle tables and
+  // DfaPlan::wsparse) take sparse_kernel; its candidate walks apply the W rules
+  // and the context accepts.  UGPU_SPARSE=0: the dense-pattern kernels
+  const bool sparse = (t.filter || p.lb || p.wsparse) && t.format == FMT_BYTE && !knob_off("UGPU_SPARSE");
+  // wfind_kernel: context accepts without a prefilter, wide tables, lookahead,
+  // and option W where no other kernel applies its rules
+  const bool wfind = (p.amode && !sparse) || t.format == FMT_WIDE || t.lookahead || (r.wmode == W_EXACT && !sparse);
+  // xc_kernel: two-state tables, and (U mode) code-point run tables -- which
+  // tables.cpp builds only for tables that are not two-state -- also where the
+  // table has a gap transducer (C4 \w+: U mode 2.30 ms, xg_kernel 2.94 ms;
+  // DESIGN 3.2.4).  Under option W only with the plan's xcw / wplus.
+  const bool xc = t.xc && !t.filter && !p.lb && t.cap1 != 0 && (!p.wtab || p.xcw) && !knob_off("UGPU_XC");
+  const bool xu = p.xu && (!p.wtab || p.wplus) && !knob_off("UGPU_XU");
+  // the table's kernel behind xc_kernel: COUNT scans of immediate tables on
+  // xi_kernel, of gap tables on xg_kernel, their records on dense_kernel
+  r.uslow.k = p.xid && !knob_off("UGPU_XI") ? K_XI : p.xg && !knob_off("UGPU_XG") ? K_XG : K_DENSE;
+  r.count.k = wfind ? K_WFIND : sparse ? K_SPARSE : xc ? K_XC : xu ? K_XU : r.uslow.k;
+  r.count.w = r.wmode == W_EXACT || r.wmode == W_XC;
+  // option W on \w+: U mode checks the run edges itself, one pass instead of
+  // isutf8 + the non-W kernel (UGPU_XUW=0 keeps those)
+  if (r.wmode == W_PLUS && r.count.k == K_XU && !knob_off("UGPU_XUW")) r.count.u = U_EDGE;
+  // the n-gram kernel, on wfind_kernel's records and passes, for tables that
+  // would scan on dense_kernel or wfind_kernel
+  r.ngram = !knob_off("UGPU_NG") && t.ng_n >= 2 && t.format != FMT_BYTE && !p.amode && !p.nul && !t.lookahead &&
+            !t.redo && t.start < t.accb && t.ng_density <= kNgramBound &&
+            (r.count.k == K_DENSE || r.count.k == K_WFIND);
+  const Step wexact{r.ngram ? K_NGRAM : K_WFIND, true, U_FAST};
+  const bool wredo = r.wmode == W_PLUS || r.wmode == W_XC;
+  if (r.ngram && !wredo) r.count.k = K_NGRAM;
+  r.record = record_kernel(r.count.k);
+  r.umix = r.count;
+  r.umix.u |= U_EXACT;
+  r.wslow = wredo ? wexact : r.count;
+  return r;
 }
+
+bool plan_ngram(const DfaTables& t, const DfaPlan& p) { return dfa_route(t, p).ngram; }
 
 void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* out)
 {
@@ -354,9 +368,10 @@ void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* out)
   info->shape = (t.finite ? UGPU_SHAPE_FINITE : 0u) | (t.word_cond_edges ? UGPU_SHAPE_WORD_COND : 0u) |
                 (t.cap1 != 0 && !t.anchored ? UGPU_SHAPE_ONE_ACCEPT : 0u) | (p.lb ? UGPU_SHAPE_LOOP_NEEDLE : 0u) |
                 (t.lookahead ? UGPU_SHAPE_LOOKAHEAD : 0u) | (plan_filter2(t, p) ? UGPU_SHAPE_FILTER2 : 0u);
-  info->kernel = base_kernel(t, p);
-  if (plan_ngram(t, p)) {
-    info->kernel = 7u;
+  const Route r = dfa_route(t, p);
+  info->kernel = r.count.k;
+  if (r.ngram) {
+    info->kernel = K_NGRAM;  // (also where option W's fast paths scan first and the n-gram kernel redoes)
     info->shape |= UGPU_SHAPE_NGRAM;
     info->prefilter_ppm = (uint32_t)(t.ng_density * 1e6) + 1;
   }
@@ -408,6 +423,9 @@ int ugpu_tables_build_host(const uint32_t* opc, uint32_t nop, ugpu_dfa_info* inf
   info->shape = (t.finite ? UGPU_SHAPE_FINITE : 0u) | (t.word_cond_edges ? UGPU_SHAPE_WORD_COND : 0u) |
                 (t.cap1 != 0 && !t.anchored ? UGPU_SHAPE_ONE_ACCEPT : 0u) |
                 (plan_filter2(t, dfa_plan(t, 0)) ? UGPU_SHAPE_FILTER2 : 0u);
+  // (the tables alone, without a plan: dfa_info_fill(t, dfa_plan(t, 0)) differs
+  // from this, first on the "lookahead" entry of tests/golden/patterns.json --
+  // kernel 4 and UGPU_SHAPE_LOOKAHEAD there, 1 and no such bit here)
   info->kernel = (t.filter && t.format == FMT_BYTE) ? 0u
                  : t.format == FMT_WIDE              ? 4u
                  : (t.xc && t.cap1 != 0)             ? 5u

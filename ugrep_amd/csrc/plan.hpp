@@ -56,6 +56,56 @@ bool plan_filter2(const DfaTables& t, const DfaPlan& p);
 // W, on wfind_kernel (kernel 4), and whose filter is selective
 // (ng_density <= kNgramBound).  UGPU_NG=0, read per call, turns it off.
 bool plan_ngram(const DfaTables& t, const DfaPlan& p);
+
+// The scan kernels, numbered as ugpu_dfa_info::kernel reports them
+enum Kernel : uint8_t { K_SPARSE = 0, K_DENSE = 1, K_XI = 2, K_XG = 3, K_WFIND = 4, K_XC = 5, K_XU = 6, K_NGRAM = 7 };
+constexpr int kKernels = 8;
+// xc_kernel's U mode (K_XU) variants: the exact main loop in the fast one's
+// place, and the run-edge check of option W on \w+
+enum : uint8_t { U_FAST = 0, U_EXACT = 1, U_EDGE = 2 };
+
+// One step of a scan: a kernel over the whole range, then the stitch
+struct Step {
+  Kernel k = K_DENSE;
+  bool w = false;      // the kernel applies the option-W rules (the word table is passed)
+  uint8_t u = U_FAST;  // K_XU only
+};
+inline bool operator==(const Step& a, const Step& b) { return a.k == b.k && a.w == b.w && a.u == b.u; }
+inline bool operator!=(const Step& a, const Step& b) { return !(a == b); }
+
+// How option W is served: by every kernel of the route itself (W_EXACT), by
+// non-W kernels on valid UTF-8 for tables equivalent to \w+ (W_PLUS, DESIGN
+// 3.8), or by xc_kernel on ASCII input (W_XC); the last two redo on `wslow`
+enum WMode : uint8_t { W_NONE, W_EXACT, W_PLUS, W_XC };
+
+// The kernels a table's scans run (DESIGN "kernel routes")
+struct Route {
+  Step count;               // a COUNT scan
+  Kernel record = K_DENSE;  // writes its records: count.k, or dense_kernel after xi / xg
+  WMode wmode = W_NONE;
+  bool ngram = false;       // the n-gram kernel stands in for dense_kernel / wfind_kernel (plan_ngram)
+  // where a range is redone when its scan flags
+  Step umix;   // UGPU_FLAG_UMIX: U mode's exact kernel
+  Step wslow;  // UGPU_FLAG_WSLOW (W_PLUS: or USLOW, or a first step off the fast path): the exact W kernel
+  Step uslow;  // UGPU_FLAG_USLOW: the table's kernel behind xc_kernel (xi / xg / dense)
+};
+// the kernel that writes the records of a COUNT scan on k
+constexpr Kernel record_kernel(Kernel k) { return k == K_XI || k == K_XG ? K_DENSE : k; }
+// The route of a table under its plan.  Reads the test knobs when it is called:
+// UGPU_SPARSE, UGPU_XI, UGPU_XG, UGPU_XC, UGPU_XU, UGPU_XUW, UGPU_NG (= 0: that
+// kernel is off).  A scanner still demotes a kernel whose occupancy is 0.
+Route dfa_route(const DfaTables& t, const DfaPlan& p);
+// r without kernel k (K_XI, K_XG, K_XC or K_XU: its occupancy on the device is
+// 0): dense_kernel in xi / xg's place, the kernel behind it in xc_kernel's
+inline Route route_demote(Route r, Kernel k)
+{
+  if (r.uslow.k == k) r.uslow.k = K_DENSE;
+  if (r.count.k == k) r.count.k = r.uslow.k, r.count.u = U_FAST;
+  r.record = record_kernel(r.count.k);
+  r.umix = r.count;
+  r.umix.u |= U_EXACT;
+  return r;
+}
 // ugpu_dfa_info from the tables and the plan (ugpu_dfa_plan_host, ugpu_dfa_info_get)
 void dfa_info_fill(const DfaTables& t, const DfaPlan& p, void* info /* ugpu_dfa_info* */);
 // \w+ as ugpu_compile builds it
