@@ -202,20 +202,9 @@ namespace {
 // Per-call scratch beside the per-wave counts and prefixes: the packed lines
 // of the starts and of the bounds.
 struct SplitWs : WaveWs {
-  uint64_t ln_cap = 0;
-  uint64_t* d_ln = nullptr;
+  DevBuf<uint64_t> d_ln;
 
-  hipError_t reserve_lines(uint64_t k)
-  {
-    if (k <= ln_cap) return hipSuccess;
-    (void)hipFree(d_ln);
-    d_ln = nullptr;
-    ln_cap = 0;
-    const uint64_t c = k + k / 4;
-    const hipError_t e = hipMalloc(&d_ln, c * 8);
-    if (e == hipSuccess) ln_cap = c;
-    return e;
-  }
+  hipError_t reserve_lines(uint64_t k) { return d_ln.reserve(k, k + k / 4); }
 };
 
 }  // namespace

@@ -12,6 +12,11 @@
 // The prefiltered sparse kernel serves tables with a selective three-byte
 // prefilter (tables.hpp); every other table runs the dense kernel.
 // Tables are uploaded once per ugpu_dfa (one Pattern), shared by all scanners.
+//
+// Memory: every device and pinned array here is a DevBuf / PinBuf and every
+// pooled workspace comes from WsLease (hip_host.hpp); the only allocation
+// calls in this file are the pinned block cache (pinned_get / pinned_put).
+// The UTF-8 / binary calls live in utf8.hip, ugpu_gen in gen.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -30,37 +35,10 @@
 #include <vector>
 
 #include "../../include/ugpu.h"
+#include "hip_host.hpp"
 #include "plan.hpp"
 #include "scan_kernels.hpp"
 #include "tables.hpp"
-
-// Geometry of a UTF-8 / NUL scan of the device bytes dbuf[0, len) (U.out unset).
-ugpu::Utf8Params utf8_params(const uint8_t* dbuf, uint64_t len)
-{
-  // CU count of the calling thread's device (cached per device id)
-  static std::atomic<int> cached[64];
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-  if (dev < 64 && cached[dev].load(std::memory_order_relaxed) > 0) {
-    cus = cached[dev].load(std::memory_order_relaxed);
-  } else {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
-    if (dev < 64) cached[dev].store(cus, std::memory_order_relaxed);
-  }
-  ugpu::Utf8Params U{};
-  U.head = reinterpret_cast<uintptr_t>(dbuf) & 15u;
-  U.g = dbuf - U.head;
-  U.len = len;
-  U.span = (U.head + len + 15u) & ~15ull;
-  const uint64_t tile = ugpu::utf8_tile();
-  const uint64_t tiles = (U.span + tile - 1) / tile;
-  const uint64_t want = (uint64_t)cus * 16;  // about 16 waves per CU
-  const uint64_t tpw = (tiles + want - 1) / want;
-  U.per = tpw * tile;
-  U.nwaves = (tiles + tpw - 1) / tpw;
-  return U;
-}
-
 
 using namespace ugpu;
 
@@ -72,16 +50,17 @@ struct ugpu_dfa {
   DfaPlan plan;
   int device = 0;
   uint32_t ntrans_pad = 0;
-  uint16_t* d_trans = nullptr;
-  uint32_t* d_trans32 = nullptr;  // wide tables (FMT_WIDE)
-  uint16_t* d_xtrans = nullptr;  // FIND transducer (restart-local tables on the dense path)
-  uint8_t* d_xid = nullptr;      // immediate transducer ids (xi_kernel), COUNT scans
-  uint16_t* d_xg = nullptr;      // gap transducer (xg_kernel), COUNT scans
-  uint8_t* d_xu = nullptr;       // code-point run tables (xc_kernel U mode): kXuTab bytes, then kXuBm3 dwords
-  uint8_t* d_xg_sync = nullptr;
-  uint8_t* d_cls = nullptr;
-  uint32_t* d_caps = nullptr;
-  uint32_t* d_wtab = nullptr;  // option W: Unicode Word ranges (UGPU_PAT_WORD)
+  // the tables on the device (an empty one: the table has none)
+  DevBuf<uint16_t> d_trans;
+  DevBuf<uint32_t> d_trans32;  // wide tables (FMT_WIDE)
+  DevBuf<uint16_t> d_xtrans;   // FIND transducer (restart-local tables on the dense path)
+  DevBuf<uint8_t> d_xid;       // immediate transducer ids (xi_kernel), COUNT scans
+  DevBuf<uint16_t> d_xg;       // gap transducer (xg_kernel), COUNT scans
+  DevBuf<uint8_t> d_xu;        // code-point run tables (xc_kernel U mode): kXuTab bytes, then kXuBm3 dwords
+  DevBuf<uint8_t> d_xg_sync;   // xg_sync, then the xg2 byte classes
+  DevBuf<uint8_t> d_cls;       // cls, then the xc byte classes
+  DevBuf<uint32_t> d_caps;
+  DevBuf<uint32_t> d_wtab;     // option W: Unicode Word ranges (UGPU_PAT_WORD)
   uint32_t nwtab = 0;
   // option W on a table equivalent to \w+: on valid UTF-8 the W
   // rules remove nothing, so such scans run the non-W kernels (xg_kernel)
@@ -94,17 +73,17 @@ struct ugpu_dfa {
   // or matches the empty string under N; its scans run the context walk
   // (wfind_kernel, device_common.hpp kWalkCtx) on the per-context accepts
   bool nul = false, amode = false;
-  uint32_t* d_acap = nullptr;  // acap, or (word boundaries) acap_rows then acap_map
+  DevBuf<uint32_t> d_acap;  // acap, or (word boundaries) acap_rows then acap_map
   // no match starts right after a word character (ScanParams::wstart)
   bool wstart = false;
   // loop-needle tables (C+N, ScanParams::lb_cls): the prefilter finds N, and
   // each candidate walks back to its C-run's start (host_api.cpp loop_needle)
   bool lb = false;
   uint8_t lb_ft[20] = {};
-  uint32_t* d_lbcls = nullptr;  // 256-bit mask of C
-  uint32_t* d_dom = nullptr;    // dominated restarts (tables.hpp dom), or NULL
-  uint32_t* d_look = nullptr;   // lookahead TAIL / HEAD masks per state (tables.hpp look), or NULL
-  uint32_t* d_ngram = nullptr;  // the n-gram bitmap (tables.hpp ng_bitmap; ngram_kernel), or NULL
+  DevBuf<uint32_t> d_lbcls;  // 256-bit mask of C
+  DevBuf<uint32_t> d_dom;    // dominated restarts (tables.hpp dom), or NULL
+  DevBuf<uint32_t> d_look;   // lookahead TAIL / HEAD masks per state (tables.hpp look), or NULL
+  DevBuf<uint32_t> d_ngram;  // the n-gram bitmap (tables.hpp ng_bitmap; ngram_kernel), or NULL
   // idle scanners of ugpu_find_all calls on this table (reused: creating one
   // costs device allocations and property queries)
   std::mutex pool_mu;
@@ -141,21 +120,20 @@ struct ugpu_scanner {
   uint32_t bol0 = 1;        // dbuf[0] begins a line (ugpu_scanner_context; anchored tables)
   const uint8_t* last_buf = nullptr;
   uint64_t last_args[5] = {0, 0, 0, 0, 0};  // lo, hi, read_end, at_eof, bias of the last scan
-  BlockRec* d_recs = nullptr;
-  uint64_t* d_entries = nullptr;
-  uint64_t* d_obase = nullptr;
+  DevBuf<BlockRec> d_recs;
+  DevBuf<uint64_t> d_entries;
+  DevBuf<uint64_t> d_obase;
   // xc_kernel COUNT passes of record scanners also write the In bits
   // (ScanParams::inbits) unless UGPU_XC_BITMAP=0; OFFSETS then expands them
-  uint16_t* d_inbits = nullptr;
-  uint64_t inbits_cap = 0;  // bytes
-  uint64_t* d_fix = nullptr;  // xc_kernel OFFSETS: per wave, the record whose start an earlier wave wrote
-  OpenRec* d_open = nullptr;  // sparse_kernel: per wave, its open walk (walk truncation)
-  uint32_t* d_susp = nullptr;  // sparse_kernel: per wave, suspended at a long walk (resume launch)
-  SuspRec* d_srec = nullptr;   // ... and its suspended state
-  DevTotals* d_tot = nullptr;
-  uint32_t* d_flags = nullptr;
-  DevTotals* h_tot = nullptr;  // pinned
-  uint32_t* h_flags = nullptr;
+  DevBuf<uint8_t> d_inbits;
+  DevBuf<uint64_t> d_fix;   // xc_kernel OFFSETS: per wave, the record whose start an earlier wave wrote
+  DevBuf<OpenRec> d_open;   // sparse_kernel: per wave, its open walk (walk truncation)
+  DevBuf<uint32_t> d_susp;  // sparse_kernel: per wave, suspended at a long walk (resume launch)
+  DevBuf<SuspRec> d_srec;   // ... and its suspended state
+  DevBuf<DevTotals> d_tot;
+  DevBuf<uint32_t> d_flags;
+  PinBuf<DevTotals> h_tot;
+  PinBuf<uint32_t> h_flags;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t stream = nullptr;
   ScanParams last{};
@@ -164,39 +142,24 @@ struct ugpu_scanner {
   // forest FIND (forest.hip): scratch, allocated on first use, and whether the
   // last scan was resolved by it (its OFFSETS pass then runs the forest too)
   bool forest = false;
-  uint64_t f_cap = 0;  // chain positions the scratch covers
-  uint32_t* d_fex = nullptr;
-  uint64_t* d_fvar = nullptr;  // entry, run[3]
-  uint64_t* d_fent = nullptr;
-  uint64_t* d_fsum = nullptr;
-  uint64_t* d_fbase = nullptr;
+  DevBuf<uint32_t> d_fex;  // (its capacity: the chain positions the scratch covers)
+  DevBuf<uint64_t> d_fvar;  // entry, run[3]
+  DevBuf<uint64_t> d_fent;
+  DevBuf<uint64_t> d_fsum;
+  DevBuf<uint64_t> d_fbase;
   // single-pass OFFSETS (sparse tables): the COUNT pass stages each wave's
   // records (ugpu_scanner_stage, or a ugpu_find_all in OFFSETS mode)
   bool stage = false, stage_once = false, staged_last = false;
-  uint64_t* d_st_start = nullptr;
-  uint32_t* d_st_len = nullptr;
-  uint32_t* d_st_cap = nullptr;
-  uint32_t* d_st_n = nullptr;
+  DevBuf<uint64_t> d_st_start;
+  DevBuf<uint32_t> d_st_len;
+  DevBuf<uint32_t> d_st_cap;
+  DevBuf<uint32_t> d_st_n;
 };
 
 namespace {
 
 const char* const kBudgetMsg =
     "the FIND chains of this table do not resynchronise on this input (stitch budget exceeded): use the CPU matcher";
-
-// (the error string lives in the host library, libugpu_host.so: ugpu_last_error)
-int fail(int code, const std::string& msg) { return ugpu::host_fail(code, msg); }
-
-int hip_fail(hipError_t e, const char* what)
-{
-  return ugpu::host_fail(UGPU_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define HIP_TRY(expr)                              \
-  do {                                             \
-    hipError_t _e = (expr);                        \
-    if (_e != hipSuccess) return hip_fail(_e, #expr); \
-  } while (0)
 
 // Process exit.  A caller may release handles from its own static
 // destructors (ugrep keeps its matcher in a global unique_ptr,
@@ -263,8 +226,6 @@ uint32_t fix_rounds_for(const ScanParams& P)
   if (r > 16) r = 16;
   return (uint32_t)r;
 }
-
-int utf8_scan(const uint8_t* dbuf, uint64_t len, bool nul, uint64_t* pos, void* stream);
 
 bool on_xc(Step step) { return step.k == K_XC || step.k == K_XU; }
 
@@ -397,26 +358,13 @@ hipError_t launch_main(const ugpu_scanner* s, Kernel k, const ScanParams& P, boo
   return kKernel[k].launch(P, s->dfa->t.format, write, s->ks[k].smem, st);
 }
 
-bool is_device_ptr(const void* p)
-{
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice;
-}
-
 void forest_free(ugpu_scanner* s)
 {
-  (void)hipFree(s->d_fex);
-  (void)hipFree(s->d_fvar);
-  (void)hipFree(s->d_fent);
-  (void)hipFree(s->d_fsum);
-  (void)hipFree(s->d_fbase);
-  s->d_fex = nullptr;
-  s->d_fvar = s->d_fent = s->d_fsum = s->d_fbase = nullptr;
-  s->f_cap = 0;
+  s->d_fex.release();
+  s->d_fvar.release();
+  s->d_fent.release();
+  s->d_fsum.release();
+  s->d_fbase.release();
 }
 
 // Forest FIND over chain positions [entry, P.hi) of P's buffer (COUNT, or
@@ -428,17 +376,16 @@ int forest_run(ugpu_scanner* s, ScanParams P, uint64_t entry, bool write, hipStr
   uint64_t pos = range < kFChunk ? range : kFChunk;
   pos = (pos + fb - 1) / fb * fb;
   if (pos == 0) pos = fb;
-  if (pos > s->f_cap) {
+  if (pos > s->d_fex.cap) {
     forest_free(s);
     const uint64_t nb = pos / fb;
     hipError_t e;
-    if ((e = hipMalloc(&s->d_fex, pos * 4)) != hipSuccess || (e = hipMalloc(&s->d_fvar, 4 * 8)) != hipSuccess ||
-        (e = hipMalloc(&s->d_fent, nb * 8)) != hipSuccess || (e = hipMalloc(&s->d_fsum, nb * 24)) != hipSuccess ||
-        (e = hipMalloc(&s->d_fbase, nb * 8)) != hipSuccess) {
+    if ((e = s->d_fex.alloc(pos)) != hipSuccess || (e = s->d_fvar.alloc(4)) != hipSuccess ||
+        (e = s->d_fent.alloc(nb)) != hipSuccess || (e = s->d_fsum.alloc(3 * nb)) != hipSuccess ||
+        (e = s->d_fbase.alloc(nb)) != hipSuccess) {
       forest_free(s);
       return hip_fail(e, "forest scratch");
     }
-    s->f_cap = pos;
   }
   UGPU_TRACE("forest entry %llu hi %llu rend %llu write %d\n", (unsigned long long)entry,
              (unsigned long long)P.hi, (unsigned long long)P.rend, (int)write);
@@ -550,112 +497,60 @@ int ugpu_dfa_create(const uint32_t* opc, uint32_t nop, uint32_t pattern_flags, u
   d->ntrans_pad = (uint32_t)((n + 7) & ~size_t(7));
   std::vector<uint16_t> tr(d->ntrans_pad, 0);
   std::copy(d->t.trans.begin(), d->t.trans.end(), tr.begin());
-  if ((e = hipMalloc(&d->d_trans, tr.size() * 2)) != hipSuccess ||
-      (e = hipMalloc(&d->d_cls, 512)) != hipSuccess ||  // cls, then the xc byte classes
-      (e = hipMalloc(&d->d_caps, d->t.caps.size() * 4)) != hipSuccess ||
-      (e = hipMemcpy(d->d_trans, tr.data(), tr.size() * 2, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d->d_cls, d->t.cls.data(), 256, hipMemcpyHostToDevice)) != hipSuccess ||
-      (e = hipMemcpy(d->d_cls + 256, d->t.xc ? d->t.xc_tab.data() : d->t.cls.data(), 256, hipMemcpyHostToDevice)) !=
-          hipSuccess ||
-      (e = hipMemcpy(d->d_caps, d->t.caps.data(), d->t.caps.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) {
+  // every failure below releases what was uploaded so far
+  auto bad = [&](const char* what) {
     ugpu_dfa_destroy(d);
-    return hip_fail(e, "table upload");
-  }
-  if (d->lb && ((e = hipMalloc(&d->d_lbcls, 32)) != hipSuccess ||
-                (e = hipMemcpy(d->d_lbcls, lbcls, 32, hipMemcpyHostToDevice)) != hipSuccess)) {
-    ugpu_dfa_destroy(d);
-    return hip_fail(e, "loop class upload");
-  }
-  if (d->t.lookahead &&
-      ((e = hipMalloc(&d->d_look, d->t.look.size() * 4)) != hipSuccess ||
-       (e = hipMemcpy(d->d_look, d->t.look.data(), d->t.look.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)) {
-    ugpu_dfa_destroy(d);
-    return hip_fail(e, "lookahead upload");
-  }
+    return hip_fail(e, what);
+  };
+  // (d_cls: cls, then the xc byte classes)
+  if ((e = d->d_trans.upload(tr.data(), tr.size())) != hipSuccess ||
+      (e = d->d_cls.upload(d->t.cls.data(), 256, d->t.xc ? d->t.xc_tab.data() : d->t.cls.data(), 256)) != hipSuccess ||
+      (e = d->d_caps.upload(d->t.caps.data(), d->t.caps.size())) != hipSuccess)
+    return bad("table upload");
+  if (d->lb && (e = d->d_lbcls.upload(lbcls, 8)) != hipSuccess) return bad("loop class upload");
+  if (d->t.lookahead && (e = d->d_look.upload(d->t.look.data(), d->t.look.size())) != hipSuccess)
+    return bad("lookahead upload");
   // (UGPU_DOM=0: no dominated-restart skips; testing)
   const char* domenv = std::getenv("UGPU_DOM");
   if (!d->t.dom.empty() && !(domenv && domenv[0] == '0') &&
-      ((e = hipMalloc(&d->d_dom, d->t.dom.size() * 4)) != hipSuccess ||
-       (e = hipMemcpy(d->d_dom, d->t.dom.data(), d->t.dom.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)) {
-    ugpu_dfa_destroy(d);
-    return hip_fail(e, "dominance upload");
-  }
+      (e = d->d_dom.upload(d->t.dom.data(), d->t.dom.size())) != hipSuccess)
+    return bad("dominance upload");
   // the n-gram bitmap, for every table that has one and may take kernel 7
   // (UGPU_NG is read again when a scanner is created)
   if (d->t.ng_n >= 2 && d->t.format != FMT_BYTE &&
-      ((e = hipMalloc(&d->d_ngram, d->t.ng_bitmap.size() * 4)) != hipSuccess ||
-       (e = hipMemcpy(d->d_ngram, d->t.ng_bitmap.data(), d->t.ng_bitmap.size() * 4, hipMemcpyHostToDevice)) !=
-           hipSuccess)) {
-    ugpu_dfa_destroy(d);
-    return hip_fail(e, "n-gram bitmap upload");
-  }
-  if (d->t.format == FMT_WIDE &&
-      ((e = hipMalloc(&d->d_trans32, d->t.trans32.size() * 4)) != hipSuccess ||
-       (e = hipMemcpy(d->d_trans32, d->t.trans32.data(), d->t.trans32.size() * 4, hipMemcpyHostToDevice)) !=
-           hipSuccess)) {
-    ugpu_dfa_destroy(d);
-    return hip_fail(e, "wide table upload");
-  }
-  if (d->amode &&
-      ((e = hipMalloc(&d->d_acap, d->t.ctx_word ? (d->t.acap_rows.size() + d->t.acap_map.size()) * 4
-                                                : d->t.acap.size() * 4)) != hipSuccess ||
-       (e = d->t.ctx_word
-                ? hipMemcpy(d->d_acap, d->t.acap_rows.data(), d->t.acap_rows.size() * 4, hipMemcpyHostToDevice)
-                : hipMemcpy(d->d_acap, d->t.acap.data(), d->t.acap.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-       (d->t.ctx_word &&
-        (e = hipMemcpy(d->d_acap + d->t.acap_rows.size(), d->t.acap_map.data(), d->t.acap_map.size() * 4,
-                       hipMemcpyHostToDevice)) != hipSuccess))) {
-    // the per-context accepts; every scan runs the context walk (no transducers)
-    ugpu_dfa_destroy(d);
-    return hip_fail(e, "context accept upload");
-  }
+      (e = d->d_ngram.upload(d->t.ng_bitmap.data(), d->t.ng_bitmap.size())) != hipSuccess)
+    return bad("n-gram bitmap upload");
+  if (d->t.format == FMT_WIDE && (e = d->d_trans32.upload(d->t.trans32.data(), d->t.trans32.size())) != hipSuccess)
+    return bad("wide table upload");
+  // the per-context accepts; every scan runs the context walk (no transducers)
+  if (d->amode && (e = d->t.ctx_word ? d->d_acap.upload(d->t.acap_rows.data(), d->t.acap_rows.size(),
+                                                         d->t.acap_map.data(), d->t.acap_map.size())
+                                     : d->d_acap.upload(d->t.acap.data(), d->t.acap.size())) != hipSuccess)
+    return bad("context accept upload");
   if (pl.wtab || (d->amode && d->t.ctx_word)) {
     // (option W, and word-boundary meta edges: both test Unicode word characters)
     std::vector<uint32_t> wt;
     ugpu_word_ranges(wt);
     d->nwtab = (uint32_t)(wt.size() / 2);
-    if ((e = hipMalloc(&d->d_wtab, wt.size() * 4)) != hipSuccess ||
-        (e = hipMemcpy(d->d_wtab, wt.data(), wt.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) {
-      ugpu_dfa_destroy(d);
-      return hip_fail(e, "word table upload");
-    }
+    if ((e = d->d_wtab.upload(wt.data(), wt.size())) != hipSuccess) return bad("word table upload");
   }
   if (pl.xtrans) {
     std::vector<uint16_t> xt(d->ntrans_pad, 0);
     std::copy(d->t.xtrans.begin(), d->t.xtrans.end(), xt.begin());
-    if ((e = hipMalloc(&d->d_xtrans, xt.size() * 2)) != hipSuccess ||
-        (e = hipMemcpy(d->d_xtrans, xt.data(), xt.size() * 2, hipMemcpyHostToDevice)) != hipSuccess) {
-      ugpu_dfa_destroy(d);
-      return hip_fail(e, "transducer table upload");
-    }
+    if ((e = d->d_xtrans.upload(xt.data(), xt.size())) != hipSuccess) return bad("transducer table upload");
   }
-  if (pl.xid) {
-    if ((e = hipMalloc(&d->d_xid, d->t.xid.size())) != hipSuccess ||
-        (e = hipMemcpy(d->d_xid, d->t.xid.data(), d->t.xid.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-      ugpu_dfa_destroy(d);
-      return hip_fail(e, "immediate transducer upload");
-    }
-  }
-  if (pl.xu) {
-    if ((e = hipMalloc(&d->d_xu, kXuTab + 4 * kXuBm3)) != hipSuccess ||
-        (e = hipMemcpy(d->d_xu, d->t.xu_tab.data(), kXuTab, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d->d_xu + kXuTab, d->t.xu_bm3.data(), 4 * kXuBm3, hipMemcpyHostToDevice)) != hipSuccess) {
-      ugpu_dfa_destroy(d);
-      return hip_fail(e, "code-point run table upload");
-    }
-  }
+  if (pl.xid && (e = d->d_xid.upload(d->t.xid.data(), d->t.xid.size())) != hipSuccess)
+    return bad("immediate transducer upload");
+  if (pl.xu && (e = d->d_xu.upload(d->t.xu_tab.data(), kXuTab, reinterpret_cast<const uint8_t*>(d->t.xu_bm3.data()),
+                                   4 * kXuBm3)) != hipSuccess)
+    return bad("code-point run table upload");
   if (pl.xg) {
     // device form: the class-major product table (tables.hpp xg2), padded to 8 entries
     std::vector<uint16_t> xg((d->t.xg2.size() + 7) & ~size_t(7), 0);
     std::copy(d->t.xg2.begin(), d->t.xg2.end(), xg.begin());
-    if ((e = hipMalloc(&d->d_xg, xg.size() * 2)) != hipSuccess ||
-        (e = hipMemcpy(d->d_xg, xg.data(), xg.size() * 2, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMalloc(&d->d_xg_sync, 512)) != hipSuccess ||
-        (e = hipMemcpy(d->d_xg_sync, d->t.xg_sync.data(), 256, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d->d_xg_sync + 256, d->t.xg2_cls.data(), 256, hipMemcpyHostToDevice)) != hipSuccess) {
-      ugpu_dfa_destroy(d);
-      return hip_fail(e, "gap transducer upload");
-    }
+    if ((e = d->d_xg.upload(xg.data(), xg.size())) != hipSuccess ||
+        (e = d->d_xg_sync.upload(d->t.xg_sync.data(), 256, d->t.xg2_cls.data(), 256)) != hipSuccess)
+      return bad("gap transducer upload");
   }
   *out = d;
   return UGPU_OK;
@@ -675,22 +570,7 @@ int ugpu_dfa_destroy(ugpu_dfa* d)
   }
   for (ugpu_scanner* s : d->pool) ugpu_scanner_destroy(s);
   for (ugpu_scanner* s : d->pool_w) ugpu_scanner_destroy(s);
-  if (d->d_trans) (void)hipFree(d->d_trans);
-  if (d->d_trans32) (void)hipFree(d->d_trans32);
-  if (d->d_xtrans) (void)hipFree(d->d_xtrans);
-  if (d->d_wtab) (void)hipFree(d->d_wtab);
-  if (d->d_xid) (void)hipFree(d->d_xid);
-  if (d->d_xg) (void)hipFree(d->d_xg);
-  if (d->d_xu) (void)hipFree(d->d_xu);
-  if (d->d_xg_sync) (void)hipFree(d->d_xg_sync);
-  if (d->d_cls) (void)hipFree(d->d_cls);
-  if (d->d_caps) (void)hipFree(d->d_caps);
-  if (d->d_acap) (void)hipFree(d->d_acap);
-  if (d->d_lbcls) (void)hipFree(d->d_lbcls);
-  if (d->d_dom) (void)hipFree(d->d_dom);
-  if (d->d_look) (void)hipFree(d->d_look);
-  if (d->d_ngram) (void)hipFree(d->d_ngram);
-  delete d;
+  delete d;  // (the tables free themselves)
   return UGPU_OK;
 }
 
@@ -735,19 +615,14 @@ int clamp_grid(int g)
 hipError_t scanner_alloc(ugpu_scanner* s, bool sparse)
 {
   hipError_t e;
-  if ((e = hipMalloc(&s->d_recs, sizeof(BlockRec) * kMaxRec)) != hipSuccess ||
-      (e = hipMalloc(&s->d_entries, sizeof(uint64_t) * kMaxRec)) != hipSuccess ||
-      (e = hipMalloc(&s->d_obase, sizeof(uint64_t) * kMaxRec)) != hipSuccess ||
-      (e = hipMalloc(&s->d_fix, sizeof(uint64_t) * kMaxRec)) != hipSuccess)
+  if ((e = s->d_recs.alloc(kMaxRec)) != hipSuccess || (e = s->d_entries.alloc(kMaxRec)) != hipSuccess ||
+      (e = s->d_obase.alloc(kMaxRec)) != hipSuccess || (e = s->d_fix.alloc(kMaxRec)) != hipSuccess)
     return e;
-  if (sparse && ((e = hipMalloc(&s->d_open, sizeof(OpenRec) * kMaxRec)) != hipSuccess ||
-                 (e = hipMalloc(&s->d_susp, sizeof(uint32_t) * kMaxRec)) != hipSuccess ||
-                 (e = hipMalloc(&s->d_srec, sizeof(SuspRec) * kMaxRec)) != hipSuccess))
+  if (sparse && ((e = s->d_open.alloc(kMaxRec)) != hipSuccess || (e = s->d_susp.alloc(kMaxRec)) != hipSuccess ||
+                 (e = s->d_srec.alloc(kMaxRec)) != hipSuccess))
     return e;
-  if ((e = hipMalloc(&s->d_tot, sizeof(DevTotals))) != hipSuccess ||
-      (e = hipMalloc(&s->d_flags, sizeof(uint32_t))) != hipSuccess ||
-      (e = hipHostMalloc(&s->h_tot, sizeof(DevTotals))) != hipSuccess ||
-      (e = hipHostMalloc(&s->h_flags, sizeof(uint32_t))) != hipSuccess ||
+  if ((e = s->d_tot.alloc(1)) != hipSuccess || (e = s->d_flags.alloc(1)) != hipSuccess ||
+      (e = s->h_tot.alloc(1)) != hipSuccess || (e = s->h_flags.alloc(1)) != hipSuccess ||
       (e = hipEventCreate(&s->ev0)) != hipSuccess || (e = hipEventCreate(&s->ev1)) != hipSuccess)
     return e;
   return hipSuccess;
@@ -760,14 +635,7 @@ hipError_t scanner_alloc(ugpu_scanner* s, bool sparse)
 void inbits_reserve(ugpu_scanner* s, uint64_t rend)
 {
   const uint64_t need = ((((rend + 15) & ~uint64_t(15)) + 2048) >> 3) + 64;
-  if (need <= s->inbits_cap) return;
-  (void)hipFree(s->d_inbits);
-  s->d_inbits = nullptr;
-  s->inbits_cap = 0;
-  if (hipMalloc(&s->d_inbits, need + need / 8) == hipSuccess)
-    s->inbits_cap = need + need / 8;
-  else
-    (void)hipGetLastError();
+  if (s->d_inbits.reserve(need, need + need / 8) != hipSuccess) (void)hipGetLastError();
 }
 
 // The table's route (plan.hpp dfa_route), minus what this device cannot run:
@@ -869,23 +737,6 @@ int scanner_create(const ugpu_dfa* dfa, ugpu_scanner** out, bool prefer_write)
 int ugpu_scanner_destroy(ugpu_scanner* s)
 {
   if (!s || exiting()) return UGPU_OK;
-  (void)hipFree(s->d_recs);
-  (void)hipFree(s->d_entries);
-  (void)hipFree(s->d_obase);
-  (void)hipFree(s->d_inbits);
-  (void)hipFree(s->d_fix);
-  (void)hipFree(s->d_open);
-  (void)hipFree(s->d_susp);
-  (void)hipFree(s->d_srec);
-  (void)hipFree(s->d_tot);
-  (void)hipFree(s->d_flags);
-  (void)hipHostFree(s->h_tot);
-  (void)hipHostFree(s->h_flags);
-  forest_free(s);
-  (void)hipFree(s->d_st_start);
-  (void)hipFree(s->d_st_len);
-  (void)hipFree(s->d_st_cap);
-  (void)hipFree(s->d_st_n);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   delete s;
@@ -941,24 +792,15 @@ int scan_step(ugpu_scanner* s, Step step, const uint8_t* dbuf, uint64_t lo, uint
     if (!s->d_st_n) {
       // all four or none (a partial failure frees what it got)
       const size_t n = (size_t)kMaxRec * kStagePer;
-      uint64_t* a = nullptr;
-      uint32_t *b = nullptr, *c = nullptr, *d = nullptr;
-      hipError_t e = hipMalloc(&a, n * 8);
-      if (e == hipSuccess) e = hipMalloc(&b, n * 4);
-      if (e == hipSuccess) e = hipMalloc(&c, n * 4);
-      if (e == hipSuccess) e = hipMalloc(&d, kMaxRec * 4);
-      if (e != hipSuccess) {
-        (void)hipFree(a);
-        (void)hipFree(b);
-        (void)hipFree(c);
-        (void)hipFree(d);
+      if (s->d_st_start.alloc(n) != hipSuccess || s->d_st_len.alloc(n) != hipSuccess ||
+          s->d_st_cap.alloc(n) != hipSuccess || s->d_st_n.alloc(kMaxRec) != hipSuccess) {
+        s->d_st_start.release();
+        s->d_st_len.release();
+        s->d_st_cap.release();
+        s->d_st_n.release();
         (void)hipGetLastError();
         return fail(UGPU_NOMEM, "staging buffers");
       }
-      s->d_st_start = a;
-      s->d_st_len = b;
-      s->d_st_cap = c;
-      s->d_st_n = d;
     }
     P.st_start = s->d_st_start;
     P.st_len = s->d_st_len;
@@ -974,7 +816,7 @@ int scan_step(ugpu_scanner* s, Step step, const uint8_t* dbuf, uint64_t lo, uint
   // 9.8 against 11.7 ms, profiles/r04_offsets_ab.txt; UGPU_XC_BITMAP=0 restores it)
   if (s->pref_write && on_xc(step) && !P.xc_w && !P.xu_w && env_u64("UGPU_XC_BITMAP", 1) != 0) {
     inbits_reserve(s, P.rend);
-    if (s->d_inbits) P.inbits = s->d_inbits;
+    P.inbits = reinterpret_cast<uint16_t*>(s->d_inbits.p);
   }
   UGPU_TRACE("scan lo %llu hi %llu rend %llu eof %d grid %u kernel %d%s\n", (unsigned long long)P.lo,
              (unsigned long long)P.hi, (unsigned long long)P.rend, at_eof, P.grid, (int)step.k, step_mode(step));
@@ -1287,121 +1129,58 @@ struct PinBlk {
 struct FindWs {
   int dev = -1;
   hipStream_t st = nullptr;
-  // ugpu_stream: the two device buffers (carry + chunk) and the pinned blocks
-  uint8_t* d_sb[2] = {nullptr, nullptr};
-  uint64_t sb_cap = 0;  // bytes of each (+ 16 padding allocated)
+  // ugpu_stream: the two device buffers (carry + chunk; 16 bytes of padding each) and the pinned blocks
+  DevBuf<uint8_t> d_sb[2];
   PinBlk pin[2];
-  uint8_t* d_in = nullptr;
-  uint64_t in_cap = 0;
-  uint64_t* d_start = nullptr;
-  uint32_t* d_len = nullptr;
-  uint32_t* d_cap = nullptr;
-  uint64_t out_cap = 0;
+  DevBuf<uint8_t> d_in;  // (16 bytes of padding)
+  DevBuf<uint64_t> d_start;
+  DevBuf<uint32_t> d_len, d_cap;
   // ugpu_find_batch: the per-input arrays of ugpu_split_matches, and its rel / line
-  uint64_t* d_seg = nullptr;
-  uint64_t seg_cap = 0;  // values
-  uint64_t* d_rl = nullptr;
-  uint64_t rl_cap = 0;   // records (two arrays)
+  DevBuf<uint64_t> d_seg;
+  DevBuf<uint64_t> d_rl;  // two arrays of n records
 
-  hipError_t reserve_in(uint64_t n)
+  hipError_t init()
   {
-    if (n <= in_cap) return hipSuccess;
-    (void)hipFree(d_in);
-    d_in = nullptr;
-    in_cap = 0;
-    const uint64_t c = n + n / 4;
-    hipError_t e = hipMalloc(&d_in, c + 16);
-    if (e == hipSuccess) in_cap = c;
+    const hipError_t e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+    if (e == hipSuccess) exit_guard_arm();
     return e;
   }
-  hipError_t reserve_out(uint64_t n)
+  hipError_t reserve_in(uint64_t n) { return d_in.reserve(n, n + n / 4, 16); }
+  // room for n records; with `keep`, the first `keep` stay (and the lists grow
+  // by halves: few copies over a sub-batch)
+  hipError_t reserve_out(uint64_t n, uint64_t keep = 0)
   {
-    if (n <= out_cap) return hipSuccess;
-    (void)hipFree(d_start);
-    (void)hipFree(d_len);
-    (void)hipFree(d_cap);
-    d_start = nullptr;
-    d_len = d_cap = nullptr;
-    out_cap = 0;
-    const uint64_t c = n + n / 4;
+    if (n <= d_cap.cap) return hipSuccess;  // (the last of the three: all have room)
+    const uint64_t m = keep ? n + n / 2 : n, c = m + m / 4;
     hipError_t e;
-    if ((e = hipMalloc(&d_start, c * 8)) != hipSuccess || (e = hipMalloc(&d_len, c * 4)) != hipSuccess ||
-        (e = hipMalloc(&d_cap, c * 4)) != hipSuccess)
-      return e;
-    out_cap = c;
-    return hipSuccess;
-  }
-  // reserve_out that keeps the first `keep` records
-  hipError_t reserve_out_keep(uint64_t n, uint64_t keep)
-  {
-    if (n <= out_cap) return hipSuccess;
-    if (!keep) return reserve_out(n);
-    uint64_t* os = d_start;
-    uint32_t *ol = d_len, *oc = d_cap;
-    d_start = nullptr;
-    d_len = d_cap = nullptr;
-    out_cap = 0;
-    hipError_t e = reserve_out(n + n / 2);  // (grows by halves: few copies over a sub-batch)
-    if (e == hipSuccess) e = hipMemcpyAsync(d_start, os, keep * 8, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_len, ol, keep * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_cap, oc, keep * 4, hipMemcpyDeviceToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFree(os);
-    (void)hipFree(ol);
-    (void)hipFree(oc);
+    if ((e = d_start.reserve_keep(n, c, keep, st)) != hipSuccess ||
+        (e = d_len.reserve_keep(n, c, keep, st)) != hipSuccess ||
+        (e = d_cap.reserve_keep(n, c, keep, st)) != hipSuccess) {
+      d_start.release();
+      d_len.release();
+      d_cap.release();
+    }
     return e;
   }
   hipError_t reserve_batch(uint64_t seg, uint64_t n)
   {
-    hipError_t e;
-    if (seg > seg_cap) {
-      (void)hipFree(d_seg);
-      d_seg = nullptr;
-      seg_cap = 0;
-      if ((e = hipMalloc(&d_seg, (seg + seg / 4) * 8)) != hipSuccess) return e;
-      seg_cap = seg + seg / 4;
-    }
-    if (n > rl_cap) {
-      (void)hipFree(d_rl);
-      d_rl = nullptr;
-      rl_cap = 0;
-      if ((e = hipMalloc(&d_rl, (n + n / 4) * 16)) != hipSuccess) return e;
-      rl_cap = n + n / 4;
-    }
-    return hipSuccess;
+    const hipError_t e = d_seg.reserve(seg, seg + seg / 4);
+    return e != hipSuccess ? e : d_rl.reserve(2 * n, 2 * (n + n / 4));
+  }
+  // Both stream buffers hold `need` bytes (doubling from 1 MiB); the `carry`
+  // bytes of buffer cur stay, in buffer 0 (cur is set to 0 when they grow).
+  hipError_t reserve_stream(uint64_t need, int& cur, uint64_t carry)
+  {
+    if (need <= d_sb[0].cap && need <= d_sb[1].cap) return hipSuccess;
+    uint64_t c = 1ull << 20;
+    while (c < need) c *= 2;
+    if (cur) std::swap(d_sb[0], d_sb[1]);
+    cur = 0;
+    const hipError_t e = d_sb[0].reserve_keep(need, c, carry, st, 16);
+    return e != hipSuccess ? e : d_sb[1].reserve(need, c, 16);
   }
 };
-
-std::mutex g_find_mu;
-std::vector<FindWs*> g_find_pool;
-
-FindWs* find_ws_acquire(int dev)
-{
-  {
-    std::lock_guard<std::mutex> lk(g_find_mu);
-    for (size_t i = 0; i < g_find_pool.size(); ++i)
-      if (g_find_pool[i]->dev == dev) {
-        FindWs* w = g_find_pool[i];
-        g_find_pool.erase(g_find_pool.begin() + (long)i);
-        return w;
-      }
-  }
-  FindWs* w = new (std::nothrow) FindWs;
-  if (!w) return nullptr;
-  w->dev = dev;
-  if (hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking) != hipSuccess) {
-    delete w;
-    return nullptr;
-  }
-  exit_guard_arm();
-  return w;
-}
-
-void find_ws_release(FindWs* w)
-{
-  std::lock_guard<std::mutex> lk(g_find_mu);
-  g_find_pool.push_back(w);
-}
+using FindPool = WsLease<FindWs>;
 
 // Every ugpu_result is the head of a ResBox: its arrays are malloc()ed, or
 // (pin set) borrowed from a pinned block of a stream's workspace
@@ -1442,6 +1221,40 @@ void scanner_release(const ugpu_dfa* dfa, ugpu_scanner* s)
   (s->pref_write ? d->pool_w : d->pool).push_back(s);
 }
 
+// the three malloc()ed arrays of a result with n records (ugpu_result_free frees them)
+bool result_arrays(ugpu_result* r, uint64_t n)
+{
+  r->start = static_cast<uint64_t*>(std::malloc(n * 8));
+  r->len = static_cast<uint32_t*>(std::malloc(n * 4));
+  r->cap = static_cast<uint32_t*>(std::malloc(n * 4));
+  return r->start && r->len && r->cap;
+}
+
+// The n records of s's last scan into the workspace's device lists, from
+// index `at` on (records before it stay); no_cap: a single-accept table's
+// scan writes no cap array.
+int records_write(ugpu_scanner* s, FindWs* ws, uint64_t n, bool no_cap, hipStream_t st, uint64_t at = 0)
+{
+  const hipError_t e = ws->reserve_out(at + n, at);
+  if (e != hipSuccess) return hip_fail(e, "match list");
+  return ugpu_scan_offsets(s, ws->d_start + at, ws->d_len + at, no_cap ? nullptr : ws->d_cap + at, n, st);
+}
+
+// records_write, then the copies into the host arrays, issued on st: the
+// caller synchronises it (and may fill hcap meanwhile when no_cap)
+int records_download(ugpu_scanner* s, FindWs* ws, uint64_t n, uint64_t* hstart, uint32_t* hlen, uint32_t* hcap,
+                     bool no_cap, hipStream_t st)
+{
+  const int rc = records_write(s, ws, n, no_cap, st);
+  if (rc) return rc;
+  hipError_t e;
+  if ((e = hipMemcpyAsync(hstart, ws->d_start, n * 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(hlen, ws->d_len, n * 4, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (!no_cap && (e = hipMemcpyAsync(hcap, ws->d_cap, n * 4, hipMemcpyDeviceToHost, st)) != hipSuccess))
+    return hip_fail(e, "hipMemcpy matches");
+  return UGPU_OK;
+}
+
 }  // namespace
 
 int ugpu_find_all(const ugpu_dfa* dfa, const uint8_t* buf, uint64_t len, uint64_t start, uint32_t mode,
@@ -1474,7 +1287,7 @@ int ugpu_find_all(const ugpu_dfa* dfa, const uint8_t* buf, uint64_t len, uint64_
     std::free(r);
     return rc;
   }
-  FindWs* ws = find_ws_acquire(dev);
+  FindWs* ws = FindPool::take(dev);
   if (!ws) {
     scanner_release(dfa, s);
     std::free(r);
@@ -1498,22 +1311,12 @@ int ugpu_find_all(const ugpu_dfa* dfa, const uint8_t* buf, uint64_t len, uint64_
   }
   if (!rc && mode == UGPU_MODE_OFFSETS && tot.count > 0) {
     const uint64_t n = tot.count;
-    r->start = static_cast<uint64_t*>(std::malloc(n * 8));
-    r->len = static_cast<uint32_t*>(std::malloc(n * 4));
-    r->cap = static_cast<uint32_t*>(std::malloc(n * 4));
-    if (!r->start || !r->len || !r->cap)
-      rc = fail(UGPU_NOMEM, "match list allocation");
-    else if ((e = ws->reserve_out(n)) != hipSuccess)
-      rc = hip_fail(e, "match list");
-    if (!rc) rc = ugpu_scan_offsets(s, ws->d_start, ws->d_len, ws->d_cap, n, ws->st);
-    if (!rc && ((e = hipMemcpyAsync(r->start, ws->d_start, n * 8, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
-                (e = hipMemcpyAsync(r->len, ws->d_len, n * 4, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
-                (e = hipMemcpyAsync(r->cap, ws->d_cap, n * 4, hipMemcpyDeviceToHost, ws->st)) != hipSuccess ||
-                (e = hipStreamSynchronize(ws->st)) != hipSuccess))
-      rc = hip_fail(e, "hipMemcpy matches");
+    if (!result_arrays(r, n)) rc = fail(UGPU_NOMEM, "match list allocation");
+    if (!rc) rc = records_download(s, ws, n, r->start, r->len, r->cap, false, ws->st);
+    if (!rc && (e = hipStreamSynchronize(ws->st)) != hipSuccess) rc = hip_fail(e, "hipMemcpy matches");
   }
   (void)hipStreamSynchronize(ws->st);
-  find_ws_release(ws);
+  FindPool::give(ws);
   scanner_release(dfa, s);
   if (rc) {
     ugpu_result_free(r);
@@ -1634,12 +1437,10 @@ void pinned_put(uint8_t* p, size_t n)
 struct RecWs {
   int dev = -1;
   hipStream_t cst = nullptr, dst = nullptr;
-  uint8_t* d_pack[2] = {nullptr, nullptr};
-  uint64_t pack_cap[2] = {0, 0};
-  uint64_t* d_esc[2] = {nullptr, nullptr};
-  uint64_t esc_cap[2] = {0, 0};
-  uint32_t* d_nesc = nullptr;  // [2]
-  uint32_t* h_nesc = nullptr;  // pinned [2]
+  DevBuf<uint8_t> d_pack[2];
+  DevBuf<uint64_t> d_esc[2];  // (index, value) pairs
+  DevBuf<uint32_t> d_nesc;    // [2]
+  PinBuf<uint32_t> h_nesc;    // [2]
   hipEvent_t packed[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
   bool used[2] = {false, false};
 
@@ -1648,65 +1449,30 @@ struct RecWs {
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&cst, hipStreamNonBlocking)) != hipSuccess ||
         (e = hipStreamCreateWithFlags(&dst, hipStreamNonBlocking)) != hipSuccess ||
-        (e = hipMalloc(&d_nesc, 2 * sizeof(uint32_t))) != hipSuccess ||
-        (e = hipHostMalloc(&h_nesc, 2 * sizeof(uint32_t))) != hipSuccess)
+        (e = d_nesc.alloc(2)) != hipSuccess || (e = h_nesc.alloc(2)) != hipSuccess)
       return e;
     for (int i = 0; i < 2; ++i)
       if ((e = hipEventCreateWithFlags(&packed[i], hipEventDisableTiming)) != hipSuccess ||
           (e = hipEventCreateWithFlags(&copied[i], hipEventDisableTiming)) != hipSuccess)
         return e;
+    exit_guard_arm();
     return hipSuccess;
+  }
+  // (only a workspace whose init() failed is ever destroyed)
+  ~RecWs()
+  {
+    for (hipStream_t q : {cst, dst})
+      if (q) (void)hipStreamDestroy(q);
+    for (hipEvent_t ev : {packed[0], packed[1], copied[0], copied[1]})
+      if (ev) (void)hipEventDestroy(ev);
   }
   hipError_t reserve(int b, uint64_t bytes, uint64_t n)
   {
-    hipError_t e;
-    if (bytes > pack_cap[b]) {
-      (void)hipFree(d_pack[b]);
-      d_pack[b] = nullptr;
-      pack_cap[b] = 0;
-      const uint64_t c = bytes + bytes / 4;
-      if ((e = hipMalloc(&d_pack[b], c)) != hipSuccess) return e;
-      pack_cap[b] = c;
-    }
-    if (n > esc_cap[b]) {
-      (void)hipFree(d_esc[b]);
-      d_esc[b] = nullptr;
-      esc_cap[b] = 0;
-      const uint64_t c = n + n / 4;
-      if ((e = hipMalloc(&d_esc[b], c * 16)) != hipSuccess) return e;
-      esc_cap[b] = c;
-    }
-    return hipSuccess;
+    const hipError_t e = d_pack[b].reserve(bytes, bytes + bytes / 4);
+    return e != hipSuccess ? e : d_esc[b].reserve(2 * n, 2 * (n + n / 4));
   }
 };
-
-std::mutex g_rec_mu;
-std::vector<RecWs*> g_rec_pool;
-
-RecWs* rec_ws_acquire(int dev)
-{
-  {
-    std::lock_guard<std::mutex> lk(g_rec_mu);
-    for (size_t i = 0; i < g_rec_pool.size(); ++i)
-      if (g_rec_pool[i]->dev == dev) {
-        RecWs* w = g_rec_pool[i];
-        g_rec_pool.erase(g_rec_pool.begin() + (long)i);
-        return w;
-      }
-  }
-  RecWs* w = new (std::nothrow) RecWs;
-  if (!w) return nullptr;
-  w->dev = dev;
-  if (w->init() != hipSuccess) return nullptr;  // (leaks the partial workspace on a broken device)
-  exit_guard_arm();
-  return w;
-}
-
-void rec_ws_release(RecWs* w)
-{
-  std::lock_guard<std::mutex> lk(g_rec_mu);
-  g_rec_pool.push_back(w);
-}
+using RecPool = WsLease<RecWs>;
 
 // H2D of a host buffer in chunks on its own thread; waiters block until a
 // prefix is on the device
@@ -1810,10 +1576,10 @@ void records_pipeline(ugpu_records* R, const ugpu_dfa* dfa, int dev, const uint8
     publish(nullptr, true);
     return;
   }
-  FindWs* ws = find_ws_acquire(dev);
-  RecWs* rw = ws ? rec_ws_acquire(dev) : nullptr;
+  FindWs* ws = FindPool::take(dev);
+  RecWs* rw = ws ? RecPool::take(dev) : nullptr;
   if (!ws || !rw) {
-    if (ws) find_ws_release(ws);
+    if (ws) FindPool::give(ws);
     scanner_release(dfa, s);
     rc = fail(UGPU_NOMEM, "records workspace");
     publish(nullptr, true);
@@ -1882,11 +1648,7 @@ void records_pipeline(ugpu_records* R, const ugpu_dfa* dfa, int dev, const uint8
       pc.n = tot.count;
       pc.dense = !R->caps && pc.n * 32 >= hi - lo && env_u64("UGPU_REC_DENSE", 1) != 0;
       const uint64_t n = pc.n, bytes = n * (pc.dense ? 2 : R->caps ? 8 : 6);
-      if ((e = ws->reserve_out(n)) != hipSuccess) {
-        rc = hip_fail(e, "records output");
-        break;
-      }
-      if ((rc = ugpu_scan_offsets(s, ws->d_start, ws->d_len, ws->d_cap, n, ws->st)) != UGPU_OK) break;
+      if ((rc = records_write(s, ws, n, false, ws->st)) != UGPU_OK) break;
       // the pack buffer b was last read by the D2H of two chunks ago
       if (rw->used[b] && (e = hipStreamWaitEvent(ws->st, rw->copied[b], 0)) != hipSuccess) {
         rc = hip_fail(e, "records event");
@@ -1991,8 +1753,8 @@ void records_pipeline(ugpu_records* R, const ugpu_dfa* dfa, int dev, const uint8
   (void)hipStreamSynchronize(ws->st);
   (void)hipStreamSynchronize(rw->dst);
   rw->used[0] = rw->used[1] = false;
-  rec_ws_release(rw);
-  find_ws_release(ws);
+  RecPool::give(rw);
+  FindPool::give(ws);
   scanner_release(dfa, s);
   if (!rc && host) rc = up.rc;
   publish(nullptr, true);
@@ -2074,29 +1836,30 @@ int ugpu_warmup(int dev)
   // the device context, one scan workspace and one records workspace (their
   // streams: a queue each), a pinned block, and one kernel launch (the
   // library's code object is loaded at the first launch)
-  FindWs* w = find_ws_acquire(dev);
+  FindWs* w = FindPool::take(dev);
   if (!w) return fail(UGPU_DEVICE, "scan workspace");
-  RecWs* r = rec_ws_acquire(dev);
+  RecWs* r = RecPool::take(dev);
   if (!r) {
-    find_ws_release(w);
+    FindPool::give(w);
     return fail(UGPU_DEVICE, "records workspace");
   }
   int rc = UGPU_OK;
-  uint8_t* d = nullptr;
-  hipError_t e = hipMalloc(&d, 64);
-  if (e == hipSuccess) e = hipMemsetAsync(d, '\n', 64, w->st);
-  if (e == hipSuccess) e = hipStreamSynchronize(w->st);
-  if (e != hipSuccess) {
-    rc = hip_fail(e, "warm-up");
-  } else {
-    uint64_t pos = 0;
-    rc = ugpu_find_nul(d, 64, &pos, w->st);
+  {
+    DevBuf<uint8_t> d;
+    hipError_t e = d.alloc(64);
+    if (e == hipSuccess) e = hipMemsetAsync(d, '\n', 64, w->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(w->st);
+    if (e != hipSuccess) {
+      rc = hip_fail(e, "warm-up");
+    } else {
+      uint64_t pos = 0;
+      rc = ugpu_find_nul(d, 64, &pos, w->st);
+    }
   }
-  if (d) (void)hipFree(d);
   size_t got = 0;
   if (uint8_t* p = pinned_get(1u << 20, got)) pinned_put(p, got);
-  rec_ws_release(r);
-  find_ws_release(w);
+  RecPool::give(r);
+  FindPool::give(w);
   return rc;
 }
 
@@ -2497,7 +2260,7 @@ void shard_scan(Shard& sh, const uint8_t* buf, uint64_t len, bool host, int src_
   }
   if ((sh.rc = dfa_on(sh.tab, sh.dev, &sh.tab)) != UGPU_OK) return;
   if ((sh.rc = scanner_acquire(sh.tab, &sh.sc)) != UGPU_OK) return;
-  if (!(sh.ws = find_ws_acquire(sh.dev))) {
+  if (!(sh.ws = FindPool::take(sh.dev))) {
     sh.rc = fail(UGPU_NOMEM, "find workspace");
     return;
   }
@@ -2546,17 +2309,10 @@ void shard_records(Shard& sh, const uint8_t* src_buf, bool src_host, int src_dev
       return;
     }
   }
-  hipError_t e;
-  if ((e = sh.ws->reserve_out(n)) != hipSuccess) {
-    sh.rc = hip_fail(e, "match list");
-    return;
-  }
-  if ((sh.rc = ugpu_scan_offsets(sh.sc, sh.ws->d_start, sh.ws->d_len, sh.ws->d_cap, n, sh.ws->st)) != UGPU_OK) return;
-  if ((e = hipMemcpyAsync(r->start + sh.base, sh.ws->d_start, n * 8, hipMemcpyDeviceToHost, sh.ws->st)) != hipSuccess ||
-      (e = hipMemcpyAsync(r->len + sh.base, sh.ws->d_len, n * 4, hipMemcpyDeviceToHost, sh.ws->st)) != hipSuccess ||
-      (e = hipMemcpyAsync(r->cap + sh.base, sh.ws->d_cap, n * 4, hipMemcpyDeviceToHost, sh.ws->st)) != hipSuccess ||
-      (e = hipStreamSynchronize(sh.ws->st)) != hipSuccess)
-    sh.rc = hip_fail(e, "hipMemcpy matches");
+  sh.rc = records_download(sh.sc, sh.ws, n, r->start + sh.base, r->len + sh.base, r->cap + sh.base, false, sh.ws->st);
+  if (sh.rc) return;
+  const hipError_t e = hipStreamSynchronize(sh.ws->st);
+  if (e != hipSuccess) sh.rc = hip_fail(e, "hipMemcpy matches");
 }
 
 }  // namespace
@@ -2617,7 +2373,7 @@ int ugpu_find_all_multi(const ugpu_dfa* dfa, const uint8_t* buf, uint64_t len, u
       if (sh.ws) {
         (void)hipSetDevice(sh.dev);
         (void)hipStreamSynchronize(sh.ws->st);
-        find_ws_release(sh.ws);
+        FindPool::give(sh.ws);
       }
       if (sh.sc) scanner_release(sh.tab, sh.sc);
     }
@@ -2667,11 +2423,7 @@ int ugpu_find_all_multi(const ugpu_dfa* dfa, const uint8_t* buf, uint64_t len, u
     r->dcap += sh.tot.dcap;
   }
   if (mode == UGPU_MODE_OFFSETS && r->count > 0) {
-    const uint64_t n = r->count;
-    r->start = static_cast<uint64_t*>(std::malloc(n * 8));
-    r->len = static_cast<uint32_t*>(std::malloc(n * 4));
-    r->cap = static_cast<uint32_t*>(std::malloc(n * 4));
-    if (!r->start || !r->len || !r->cap) {
+    if (!result_arrays(r, r->count)) {
       ugpu_result_free(r);
       return finish(fail(UGPU_NOMEM, "match list allocation"));
     }
@@ -2684,117 +2436,6 @@ int ugpu_find_all_multi(const ugpu_dfa* dfa, const uint8_t* buf, uint64_t len, u
   }
   *out = r;
   return finish(UGPU_OK);
-}
-
-// ---------------------------------------------------------------- binary detection
-namespace {
-
-// One device result slot and its pinned host copy, pooled per device.
-struct SlotWs {
-  int dev = -1;
-  uint64_t* d = nullptr;
-  uint64_t* h = nullptr;
-};
-std::mutex g_slot_mu;
-std::vector<SlotWs*> g_slot_pool;
-
-SlotWs* slot_acquire(int dev)
-{
-  {
-    std::lock_guard<std::mutex> lk(g_slot_mu);
-    for (size_t i = 0; i < g_slot_pool.size(); ++i)
-      if (g_slot_pool[i]->dev == dev) {
-        SlotWs* w = g_slot_pool[i];
-        g_slot_pool.erase(g_slot_pool.begin() + (long)i);
-        return w;
-      }
-  }
-  SlotWs* w = new (std::nothrow) SlotWs;
-  if (!w) return nullptr;
-  w->dev = dev;
-  if (hipMalloc(&w->d, 8) != hipSuccess || hipHostMalloc(&w->h, 8) != hipSuccess) {
-    (void)hipFree(w->d);
-    delete w;
-    return nullptr;
-  }
-  return w;
-}
-
-void slot_release(SlotWs* w)
-{
-  std::lock_guard<std::mutex> lk(g_slot_mu);
-  g_slot_pool.push_back(w);
-}
-
-// First failing byte of dbuf[0, len) (isutf8, or NUL with nul) or ~0.
-int utf8_scan(const uint8_t* dbuf, uint64_t len, bool nul, uint64_t* pos, void* stream)
-{
-  if (!dbuf && len) return fail(UGPU_INVAL, "NULL buffer");
-  if (!pos) return fail(UGPU_INVAL, "NULL result pointer");
-  *pos = ~0ull;
-  if (len == 0) return UGPU_OK;
-  if (!is_device_ptr(dbuf)) return fail(UGPU_INVAL, "buffer must be device memory");
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  Utf8Params U = utf8_params(dbuf, len);
-  SlotWs* w = slot_acquire(dev);
-  if (!w) return fail(UGPU_NOMEM, "result slot");
-  U.out = w->d;
-  hipError_t e;
-  int rc = UGPU_OK;
-  if ((e = hipMemsetAsync(w->d, 0xff, 8, st)) != hipSuccess || (e = launch_utf8(U, nul, st)) != hipSuccess ||
-      (e = hipMemcpyAsync(w->h, w->d, 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
-      (e = hipStreamSynchronize(st)) != hipSuccess) {
-    rc = hip_fail(e, nul ? "NUL scan" : "UTF-8 check");
-  } else {
-    *pos = *w->h == ~0ull ? ~0ull : *w->h - U.head;
-  }
-  slot_release(w);
-  return rc;
-}
-
-}  // namespace
-
-int ugpu_check_utf8(const uint8_t* dbuf, uint64_t len, uint64_t* first_bad, void* stream)
-{
-  return utf8_scan(dbuf, len, false, first_bad, stream);
-}
-
-int ugpu_find_nul(const uint8_t* dbuf, uint64_t len, uint64_t* pos, void* stream)
-{
-  return utf8_scan(dbuf, len, true, pos, stream);
-}
-
-int ugpu_is_binary(const uint8_t* dbuf, uint64_t len, uint32_t flags, int* binary, void* stream)
-{
-  if (!binary) return fail(UGPU_INVAL, "NULL result pointer");
-  *binary = 0;
-  if (flags & UGPU_BIN_INIT_WINDOW) {
-    // GrepWorker::init_is_binary (src/ugrep.cpp:3998-4015): do not judge a
-    // UTF-8 sequence cut off by the window end
-    if (len == 0) return UGPU_OK;
-    uint8_t tail[4] = {0, 0, 0, 0};
-    const uint64_t nt = len < 4 ? len : 4;
-    HIP_TRY(hipMemcpy(tail + (4 - nt), dbuf + len - nt, nt, hipMemcpyDeviceToHost));
-    const uint8_t* t = tail + 4;  // t[-1] = last byte
-    uint64_t avail = len;
-    if ((t[-1] & 0x80) == 0x80) {
-      uint64_t n = nt;
-      while (n > 0 && (t[(int64_t)(--avail) - (int64_t)len] & 0xc0) == 0x80) --n;
-      if ((t[(int64_t)avail - (int64_t)len] & 0xc0) != 0xc0) {
-        *binary = 1;
-        return UGPU_OK;
-      }
-    }
-    len = avail;
-  }
-  // is_binary (src/ugrep.cpp:699-711)
-  if (flags & UGPU_BIN_NULL_DATA) return UGPU_OK;
-  uint64_t pos = ~0ull;
-  const int rc = utf8_scan(dbuf, len, (flags & UGPU_BIN_NUL_ONLY) != 0, &pos, stream);
-  if (rc == UGPU_OK) *binary = pos != ~0ull;
-  return rc;
 }
 
 // ---------------------------------------------------------------- streaming
@@ -2824,34 +2465,8 @@ namespace {
 // ugrep's workers would wait on each other; VERDICT r4 item 6's trace)
 int stream_grow(ugpu_stream* st, uint64_t need)
 {
-  FindWs* w = st->ws;
-  if (need <= w->sb_cap) return UGPU_OK;
-  uint64_t c = w->sb_cap ? w->sb_cap : (1ull << 20);
-  while (c < need) c *= 2;
-  uint8_t* nb[2] = {nullptr, nullptr};
-  for (int i = 0; i < 2; ++i) {
-    hipError_t e = hipMalloc(&nb[i], c + 16);
-    if (e != hipSuccess) {
-      if (nb[0]) (void)hipFree(nb[0]);
-      return hip_fail(e, "stream buffer");
-    }
-  }
-  if (st->carry) {
-    hipError_t e = hipMemcpyAsync(nb[0], w->d_sb[st->cur], st->carry, hipMemcpyDeviceToDevice, w->st);
-    if (e == hipSuccess) e = hipStreamSynchronize(w->st);
-    if (e != hipSuccess) {
-      (void)hipFree(nb[0]);
-      (void)hipFree(nb[1]);
-      return hip_fail(e, "stream carry copy");
-    }
-  }
-  for (int i = 0; i < 2; ++i)
-    if (w->d_sb[i]) (void)hipFree(w->d_sb[i]);
-  w->d_sb[0] = nb[0];
-  w->d_sb[1] = nb[1];
-  st->cur = 0;
-  w->sb_cap = c;
-  return UGPU_OK;
+  const hipError_t e = st->ws->reserve_stream(need, st->cur, st->carry);
+  return e == hipSuccess ? UGPU_OK : hip_fail(e, "stream buffer");
 }
 
 // a pinned block of the workspace with no live result and room for m records
@@ -2900,7 +2515,7 @@ int ugpu_stream_create(const ugpu_dfa* dfa, uint64_t keep, ugpu_stream** out)
     delete st;
     return rc;
   }
-  st->ws = find_ws_acquire(dev);
+  st->ws = FindPool::take(dev);
   if (!st->ws) {
     scanner_release(dfa, st->sc);
     delete st;
@@ -2916,7 +2531,7 @@ int ugpu_stream_destroy(ugpu_stream* st)
   (void)hipStreamSynchronize(st->ws->st);
   st->sc->bol0 = 1;
   scanner_release(st->dfa, st->sc);
-  find_ws_release(st->ws);
+  FindPool::give(st->ws);
   delete st;
   return UGPU_OK;
 }
@@ -2946,27 +2561,19 @@ int ugpu_stream_reserve(const ugpu_dfa* dfa, int n, uint64_t feed_bytes)
     scs.push_back(s);
     // (the In bits of a COUNT pass over a whole buffer, as ugpu_scan sizes them)
     if (on_xc(s->route.count) && env_u64("UGPU_XC_BITMAP", 1) != 0) inbits_reserve(s, c + 16);
-    FindWs* w = find_ws_acquire(dev);
+    FindWs* w = FindPool::take(dev);
     if (!w) {
       rc = fail(UGPU_NOMEM, "stream workspace");
       break;
     }
     wss.push_back(w);
-    if (w->sb_cap < c) {
-      for (int k = 0; k < 2; ++k) {
-        (void)hipFree(w->d_sb[k]);
-        w->d_sb[k] = nullptr;
-      }
-      w->sb_cap = 0;
-      hipError_t e = hipMalloc(&w->d_sb[0], c + 16);
-      if (e == hipSuccess) e = hipMalloc(&w->d_sb[1], c + 16);
-      if (e != hipSuccess) {
-        rc = hip_fail(e, "stream buffer");
-        break;
-      }
-      w->sb_cap = c;
+    int cur = 0;
+    hipError_t e = w->reserve_stream(need, cur, 0);
+    if (e != hipSuccess) {
+      rc = hip_fail(e, "stream buffer");
+      break;
     }
-    hipError_t e = w->reserve_out(recs);
+    e = w->reserve_out(recs);
     if (e != hipSuccess) {
       rc = hip_fail(e, "stream match list");
       break;
@@ -2974,7 +2581,7 @@ int ugpu_stream_reserve(const ugpu_dfa* dfa, int n, uint64_t feed_bytes)
     if (env_u64("UGPU_RESERVE_PIN", 0) != 0 && !stream_pin(w, recs)) rc = fail(UGPU_NOMEM, "pinned match list");
   }
   for (ugpu_scanner* s : scs) scanner_release(dfa, s);
-  for (FindWs* w : wss) find_ws_release(w);
+  for (FindWs* w : wss) FindPool::give(w);
   return rc;
 }
 
@@ -3080,29 +2687,20 @@ int ugpu_stream_feed(ugpu_stream* st, const uint8_t* chunk, uint64_t len, int fi
       const uint64_t m = tot.count;
       const uint32_t cap1 = st->dfa->t.cap1;
       const bool one = cap1 != 0 && !st->dfa->t.anchored;
-      hipError_t e = w->reserve_out(m);
-      if (e != hipSuccess) rc = hip_fail(e, "stream match list");
-      if (!rc) rc = ugpu_scan_offsets(st->sc, w->d_start, w->d_len, one ? nullptr : w->d_cap, m, hs);
-      PinBlk* pb = rc ? nullptr : stream_pin(w, m);
+      PinBlk* pb = stream_pin(w, m);
       uint64_t* hstart = nullptr;
       uint32_t *hlen = nullptr, *hcap = nullptr;
-      if (!rc && pb) {
+      if (pb) {
         hstart = reinterpret_cast<uint64_t*>(pb->p);
         hlen = reinterpret_cast<uint32_t*>(pb->p + pb->cap * 8);
         hcap = reinterpret_cast<uint32_t*>(pb->p + pb->cap * 12);
-      } else if (!rc) {
-        hstart = static_cast<uint64_t*>(std::malloc(m * 8));
-        hlen = static_cast<uint32_t*>(std::malloc(m * 4));
-        hcap = static_cast<uint32_t*>(std::malloc(m * 4));
-        r->start = hstart;
-        r->len = hlen;
-        r->cap = hcap;
-        if (!hstart || !hlen || !hcap) rc = fail(UGPU_NOMEM, "stream match list");
+      } else {
+        if (!result_arrays(r, m)) rc = fail(UGPU_NOMEM, "stream match list");
+        hstart = r->start;
+        hlen = r->len;
+        hcap = r->cap;
       }
-      if (!rc && ((e = hipMemcpyAsync(hstart, w->d_start, m * 8, hipMemcpyDeviceToHost, hs)) != hipSuccess ||
-                  (e = hipMemcpyAsync(hlen, w->d_len, m * 4, hipMemcpyDeviceToHost, hs)) != hipSuccess ||
-                  (!one && (e = hipMemcpyAsync(hcap, w->d_cap, m * 4, hipMemcpyDeviceToHost, hs)) != hipSuccess)))
-        rc = hip_fail(e, "stream match list copy");
+      if (!rc) rc = records_download(st->sc, w, m, hstart, hlen, hcap, one, hs);
       if (!rc && one) {
         // (while the copies run)
         if (pb && pb->cap_v == cap1 && pb->cap_n >= m) {
@@ -3116,7 +2714,10 @@ int ugpu_stream_feed(ugpu_stream* st, const uint8_t* chunk, uint64_t len, int fi
       } else if (!rc && pb) {
         pb->cap_n = 0;  // (the cap array now holds copied accept indices)
       }
-      if (!rc && (e = hipStreamSynchronize(hs)) != hipSuccess) rc = hip_fail(e, "stream match list copy");
+      if (!rc) {
+        const hipError_t e = hipStreamSynchronize(hs);
+        if (e != hipSuccess) rc = hip_fail(e, "stream match list copy");
+      }
       if (rc) {
         (void)hipStreamSynchronize(hs);
         ugpu_result_free(r);
@@ -3165,14 +2766,6 @@ int ugpu_result_free(ugpu_result* r)
     std::free(r->cap);
   }
   std::free(b);
-  return UGPU_OK;
-}
-
-int ugpu_gen(int kind, uint64_t seed, uint64_t off, uint8_t* dbuf, uint64_t len, void* stream)
-{
-  if (kind < 1 || kind > 4) return fail(UGPU_INVAL, "unknown corpus kind");
-  if (!dbuf && len) return fail(UGPU_INVAL, "NULL buffer");
-  HIP_TRY(launch_gen(kind, seed, off, dbuf, len, reinterpret_cast<hipStream_t>(stream)));
   return UGPU_OK;
 }
 
@@ -3236,12 +2829,7 @@ int batch_sub(const ugpu_dfa* dfa, ugpu_scanner* s, FindWs* ws, bool table_one, 
     rc = ugpu_scan(s, ws->d_in, 0, total, total, 1, 0, ws->st);
     if (!rc) rc = ugpu_scan_totals(s, &tot);
     n = tot.count;
-    if (!rc && n) {
-      if ((e = ws->reserve_out(n)) != hipSuccess)
-        rc = hip_fail(e, "match list");
-      else
-        rc = ugpu_scan_offsets(s, ws->d_start, ws->d_len, ws->d_cap, n, ws->st);
-    }
+    if (!rc && n) rc = records_write(s, ws, n, false, ws->st);
   } else if (!rc) {
     // each input with its own whole-input semantics: its bytes of the packed
     // copy as a buffer of their own, the records biased to packed offsets
@@ -3252,10 +2840,7 @@ int batch_sub(const ugpu_dfa* dfa, ugpu_scanner* s, FindWs* ws, bool table_one, 
       rc = ugpu_scan(s, ws->d_in + bounds[k], 0, len, len, 1, bounds[k], ws->st);
       if (!rc) rc = ugpu_scan_totals(s, &tot);
       if (rc || !tot.count) continue;
-      if ((e = ws->reserve_out_keep(n + tot.count, n)) != hipSuccess)
-        rc = hip_fail(e, "match list");
-      else
-        rc = ugpu_scan_offsets(s, ws->d_start + n, ws->d_len + n, ws->d_cap + n, tot.count, ws->st);
+      rc = records_write(s, ws, tot.count, false, ws->st, n);
       n += tot.count;
     }
   }
@@ -3370,7 +2955,7 @@ int ugpu_find_batch(const ugpu_dfa* dfa, const uint8_t* const* bufs, const uint6
       if (e != hipSuccess) rc = hip_fail(e, "hipGetDevice");
       if (!rc) rc = dfa_on(dfa, dev, &dfa);
       if (!rc) rc = scanner_acquire(dfa, &s, true);
-      if (!rc && !(ws = find_ws_acquire(dev))) rc = fail(UGPU_NOMEM, "find workspace");
+      if (!rc && !(ws = FindPool::take(dev))) rc = fail(UGPU_NOMEM, "find workspace");
       if (rc) break;
     }
     bool sub_one = false;
@@ -3380,7 +2965,7 @@ int ugpu_find_batch(const ugpu_dfa* dfa, const uint8_t* const* bufs, const uint6
   }
   if (ws) {
     (void)hipStreamSynchronize(ws->st);
-    find_ws_release(ws);
+    FindPool::give(ws);
   }
   if (s) scanner_release(dfa, s);
   if (rc) {

@@ -5,6 +5,7 @@
 // stream in parallel (one thread per cell).  The byte-level specification is
 // documented with the kinds in include/ugpu.h; tests check it against the host
 // restatement in oracle/gen.h.
+#include "hip_host.hpp"
 #include "scan_kernels.hpp"
 
 namespace ugpu {
@@ -200,3 +201,12 @@ hipError_t launch_gen(int kind, uint64_t seed, uint64_t off, uint8_t* dbuf, uint
 }
 
 }  // namespace ugpu
+
+extern "C" int ugpu_gen(int kind, uint64_t seed, uint64_t off, uint8_t* dbuf, uint64_t len, void* stream)
+{
+  using namespace ugpu;
+  if (kind < 1 || kind > 4) return fail(UGPU_INVAL, "unknown corpus kind");
+  if (!dbuf && len) return fail(UGPU_INVAL, "NULL buffer");
+  HIP_TRY(launch_gen(kind, seed, off, dbuf, len, reinterpret_cast<hipStream_t>(stream)));
+  return UGPU_OK;
+}

@@ -1,25 +1,12 @@
 // line_host.hpp -- the host layer of the line calls (lines.hip, linesel.hip,
-// linebool.hip): error reporting, the wave ranges, the per-device workspace
-// pool, the newline count with its prefix, and the driver of the two selection
-// calls.
+// linebool.hip, batch.hip): the wave ranges, the per-wave workspace, the
+// newline count with its prefix, and the driver of the two selection calls.
+// Error reporting, the buffers and the workspace pool come from hip_host.hpp.
 #pragma once
-#include <mutex>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "../../include/ugpu.h"
-#include "plan.hpp"
+#include "hip_host.hpp"
 #include "scan_kernels.hpp"
 
 namespace ugpu {
-
-inline int fail(int code, const std::string& msg) { return host_fail(code, msg); }
-
-inline int hip_fail(hipError_t e, const char* what)
-{
-  return host_fail(UGPU_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 // The wave ranges of the line kernels for a buffer of len bytes: whole tiles,
 // about 16 waves per CU, at most kMaxRec.  Returns the current device, or -1
@@ -45,84 +32,31 @@ inline int line_wave_ranges(uint64_t len, uint64_t* per, uint64_t* nwaves)
   return dev;
 }
 
-// A workspace of type W (with an int dev) taken from the idle ones of its
-// device for the length of a call, so that repeated calls do no hipMalloc or
-// hipFree (hipFree synchronises the device).  Idle workspaces are kept for the
-// process lifetime.  ws is NULL when none could be made.
-template <class W>
-struct WsLease {
-  W* ws = nullptr;
-
-  explicit WsLease(int dev)
-  {
-    Pool& p = pool();
-    std::lock_guard<std::mutex> lk(p.mu);
-    for (size_t i = 0; i < p.idle.size(); ++i)
-      if (p.idle[i]->dev == dev) {
-        ws = p.idle[i];
-        p.idle.erase(p.idle.begin() + (long)i);
-        return;
-      }
-    ws = new (std::nothrow) W;
-    if (ws) ws->dev = dev;
-  }
-  ~WsLease()
-  {
-    if (!ws) return;
-    Pool& p = pool();
-    std::lock_guard<std::mutex> lk(p.mu);
-    p.idle.push_back(ws);
-  }
-  WsLease(const WsLease&) = delete;
-  WsLease& operator=(const WsLease&) = delete;
-  W* operator->() const { return ws; }
-
- private:
-  struct Pool {
-    std::mutex mu;
-    std::vector<W*> idle;
-  };
-  static Pool& pool()
-  {
-    static Pool p;
-    return p;
-  }
-};
-
 // `slots` per-wave uint64_t arrays the kernels write (d_out: array s is
 // d_out + s * nw), as many the host stitches for them (d_in), and pinned host
 // copies of both.  Grows only.
 struct WaveWs {
   int dev = -1;
-  uint64_t cap = 0;  // values each way
-  uint64_t* d_out = nullptr;
-  uint64_t* d_in = nullptr;
-  uint64_t* h_out = nullptr;
-  uint64_t* h_in = nullptr;
+  DevBuf<uint64_t> d_out, d_in;
+  PinBuf<uint64_t> h_out, h_in;
 
   void release()
   {
-    (void)hipFree(d_out);
-    (void)hipFree(d_in);
-    (void)hipHostFree(h_out);
-    (void)hipHostFree(h_in);
-    d_out = d_in = h_out = h_in = nullptr;
-    cap = 0;
+    d_out.release();
+    d_in.release();
+    h_out.release();
+    h_in.release();
   }
 
   hipError_t reserve(uint64_t nw, uint64_t slots)
   {
-    hipError_t e = hipSuccess;
-    if (nw * slots > cap) {
+    const uint64_t n = nw * slots;
+    if (n <= h_in.cap) return hipSuccess;  // (the last of the four: all have room)
+    release();
+    hipError_t e;
+    if ((e = d_out.alloc(n)) != hipSuccess || (e = d_in.alloc(n)) != hipSuccess || (e = h_out.alloc(n)) != hipSuccess ||
+        (e = h_in.alloc(n)) != hipSuccess)
       release();
-      const size_t bytes = nw * slots * 8;
-      if ((e = hipMalloc(&d_out, bytes)) != hipSuccess || (e = hipMalloc(&d_in, bytes)) != hipSuccess ||
-          (e = hipHostMalloc(&h_out, bytes)) != hipSuccess || (e = hipHostMalloc(&h_in, bytes)) != hipSuccess) {
-        release();
-        return e;
-      }
-      cap = nw * slots;
-    }
     return e;
   }
 };

@@ -235,33 +235,17 @@ namespace {
 // per-wave -c records with their pinned host copy, and quarter counts (sparse
 // mode).
 struct LinesWs : WaveWs {
-  uint64_t rec_cap = 0, q_cap = 0;
-  LineRec* d_rec = nullptr;
-  LineRec* h_rec = nullptr;
-  uint16_t* d_qc = nullptr;
+  DevBuf<LineRec> d_rec;
+  PinBuf<LineRec> h_rec;
+  DevBuf<uint16_t> d_qc;
 
   hipError_t reserve(uint64_t nw, uint64_t quarters)
   {
-    hipError_t e = WaveWs::reserve(nw, 1);
-    if (e != hipSuccess) return e;
-    if (nw > rec_cap) {
-      (void)hipFree(d_rec);
-      (void)hipHostFree(h_rec);
-      d_rec = h_rec = nullptr;
-      rec_cap = 0;
-      if ((e = hipMalloc(&d_rec, nw * sizeof(LineRec))) != hipSuccess ||
-          (e = hipHostMalloc(&h_rec, nw * sizeof(LineRec))) != hipSuccess)
-        return e;
-      rec_cap = nw;
-    }
-    if (quarters > q_cap) {
-      (void)hipFree(d_qc);
-      d_qc = nullptr;
-      q_cap = 0;
-      if ((e = hipMalloc(&d_qc, quarters * 2)) != hipSuccess) return e;
-      q_cap = quarters;
-    }
-    return e;
+    hipError_t e;
+    if ((e = WaveWs::reserve(nw, 1)) != hipSuccess || (e = d_rec.reserve(nw, nw)) != hipSuccess ||
+        (e = h_rec.reserve(nw, nw)) != hipSuccess)
+      return e;
+    return d_qc.reserve(quarters, quarters);
   }
 };
 

@@ -391,6 +391,8 @@ struct Utf8Params {
 };
 hipError_t launch_utf8(const Utf8Params& U, bool nul, hipStream_t stream);
 uint32_t utf8_tile();
+// its host call: the first failing byte of the device bytes dbuf[0, len), or ~0 (synchronises the stream)
+int utf8_scan(const uint8_t* dbuf, uint64_t len, bool nul, uint64_t* pos, void* stream);
 // option W (-w) FIND, wfind.hip: one chain record per wave (64 lane segments
 // stitched in the wave), exact W walks (device_common.hpp), records stitched
 // by fix_kernel; COUNT and OFFSETS passes

@@ -25,7 +25,13 @@
 // DPP (wave_shr) and from lane 63 to the next 1 KiB chunk.  A wave stops at its
 // first failing byte (atomicMin of the position) and when a lower position
 // has already been found.
+//
+// The host calls of the C ABI over it (ugpu_check_utf8, ugpu_find_nul,
+// ugpu_is_binary) are at the end of the file.
+#include <atomic>
+
 #include "device_common.hpp"
+#include "hip_host.hpp"
 
 namespace ugpu {
 
@@ -210,4 +216,120 @@ hipError_t launch_utf8(const Utf8Params& U, bool nul, hipStream_t stream)
 
 uint32_t utf8_tile() { return kUTile; }
 
+namespace {
+
+// Geometry of a UTF-8 / NUL scan of the device bytes dbuf[0, len) (U.out unset).
+Utf8Params utf8_params(const uint8_t* dbuf, uint64_t len)
+{
+  // CU count of the calling thread's device (cached per device id)
+  static std::atomic<int> cached[64];
+  int dev = 0, cus = 256;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
+  if (dev < 64 && cached[dev].load(std::memory_order_relaxed) > 0) {
+    cus = cached[dev].load(std::memory_order_relaxed);
+  } else {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 256;
+    if (dev < 64) cached[dev].store(cus, std::memory_order_relaxed);
+  }
+  Utf8Params U{};
+  U.head = reinterpret_cast<uintptr_t>(dbuf) & 15u;
+  U.g = dbuf - U.head;
+  U.len = len;
+  U.span = (U.head + len + 15u) & ~15ull;
+  const uint64_t tile = utf8_tile();
+  const uint64_t tiles = (U.span + tile - 1) / tile;
+  const uint64_t want = (uint64_t)cus * 16;  // about 16 waves per CU
+  const uint64_t tpw = (tiles + want - 1) / want;
+  U.per = tpw * tile;
+  U.nwaves = (tiles + tpw - 1) / tpw;
+  return U;
+}
+
+// One device result slot and its pinned host copy, pooled per device.
+struct SlotWs {
+  int dev = -1;
+  DevBuf<uint64_t> d;
+  PinBuf<uint64_t> h;
+
+  hipError_t init()
+  {
+    const hipError_t e = d.alloc(1);
+    return e != hipSuccess ? e : h.alloc(1);
+  }
+};
+
+}  // namespace
+
+// First failing byte of dbuf[0, len) (isutf8, or NUL with nul) or ~0.
+int utf8_scan(const uint8_t* dbuf, uint64_t len, bool nul, uint64_t* pos, void* stream)
+{
+  if (!dbuf && len) return fail(UGPU_INVAL, "NULL buffer");
+  if (!pos) return fail(UGPU_INVAL, "NULL result pointer");
+  *pos = ~0ull;
+  if (len == 0) return UGPU_OK;
+  if (!is_device_ptr(dbuf)) return fail(UGPU_INVAL, "buffer must be device memory");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  Utf8Params U = utf8_params(dbuf, len);
+  WsLease<SlotWs> w(dev);
+  if (!w.ws) return fail(UGPU_NOMEM, "result slot");
+  U.out = w->d;
+  hipError_t e;
+  if ((e = hipMemsetAsync(w->d, 0xff, 8, st)) != hipSuccess || (e = launch_utf8(U, nul, st)) != hipSuccess ||
+      (e = hipMemcpyAsync(w->h, w->d, 8, hipMemcpyDeviceToHost, st)) != hipSuccess ||
+      (e = hipStreamSynchronize(st)) != hipSuccess)
+    return hip_fail(e, nul ? "NUL scan" : "UTF-8 check");
+  *pos = *w->h == ~0ull ? ~0ull : *w->h - U.head;
+  return UGPU_OK;
+}
+
 }  // namespace ugpu
+
+// ---------------------------------------------------------------- C ABI
+using namespace ugpu;
+
+extern "C" {
+
+int ugpu_check_utf8(const uint8_t* dbuf, uint64_t len, uint64_t* first_bad, void* stream)
+{
+  return utf8_scan(dbuf, len, false, first_bad, stream);
+}
+
+int ugpu_find_nul(const uint8_t* dbuf, uint64_t len, uint64_t* pos, void* stream)
+{
+  return utf8_scan(dbuf, len, true, pos, stream);
+}
+
+int ugpu_is_binary(const uint8_t* dbuf, uint64_t len, uint32_t flags, int* binary, void* stream)
+{
+  if (!binary) return fail(UGPU_INVAL, "NULL result pointer");
+  *binary = 0;
+  if (flags & UGPU_BIN_INIT_WINDOW) {
+    // GrepWorker::init_is_binary (src/ugrep.cpp:3998-4015): do not judge a
+    // UTF-8 sequence cut off by the window end
+    if (len == 0) return UGPU_OK;
+    uint8_t tail[4] = {0, 0, 0, 0};
+    const uint64_t nt = len < 4 ? len : 4;
+    HIP_TRY(hipMemcpy(tail + (4 - nt), dbuf + len - nt, nt, hipMemcpyDeviceToHost));
+    const uint8_t* t = tail + 4;  // t[-1] = last byte
+    uint64_t avail = len;
+    if ((t[-1] & 0x80) == 0x80) {
+      uint64_t n = nt;
+      while (n > 0 && (t[(int64_t)(--avail) - (int64_t)len] & 0xc0) == 0x80) --n;
+      if ((t[(int64_t)avail - (int64_t)len] & 0xc0) != 0xc0) {
+        *binary = 1;
+        return UGPU_OK;
+      }
+    }
+    len = avail;
+  }
+  // is_binary (src/ugrep.cpp:699-711)
+  if (flags & UGPU_BIN_NULL_DATA) return UGPU_OK;
+  uint64_t pos = ~0ull;
+  const int rc = utf8_scan(dbuf, len, (flags & UGPU_BIN_NUL_ONLY) != 0, &pos, stream);
+  if (rc == UGPU_OK) *binary = pos != ~0ull;
+  return rc;
+}
+
+}  // extern "C"
