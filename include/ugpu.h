@@ -352,7 +352,11 @@ int ugpu_scan_totals(ugpu_scanner *sc, ugpu_totals *out);
    into device arrays (capacity entries each) on `stream`.  d_cap may be NULL
    for a table with one accept index (ugpu_dfa_info.accepting states all take
    the same index; the records are then 12 bytes: start, len) -- the accept
-   index of every record is that index; UGPU_INVAL for other tables. */
+   index of every record is that index; UGPU_INVAL for other tables.
+   UGPU_UNSUPPORTED when a match of the scan is 2^32 bytes or longer (its
+   length does not fit a record; the totals of the COUNT scan stay valid):
+   no record of such a scan is to be used.  ugpu_find_all in OFFSETS mode and
+   the other record-returning calls return the same. */
 int ugpu_scan_offsets(ugpu_scanner *sc, uint64_t *d_start, uint32_t *d_len, uint32_t *d_cap, uint64_t capacity,
                       void *stream);
 /* Shard-boundary stitch: the scan of [lo,hi) assumed the chain entered at

@@ -133,6 +133,8 @@ struct ugpu_scanner {
   DevBuf<DevTotals> d_tot;
   DevBuf<uint32_t> d_flags;
   PinBuf<DevTotals> h_tot;
+  DevBuf<uint64_t> d_rdg;  // digest of the written records (ugpu_scan_offsets' length check)
+  PinBuf<uint64_t> h_rdg;
   PinBuf<uint32_t> h_flags;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipStream_t stream = nullptr;
@@ -623,6 +625,7 @@ hipError_t scanner_alloc(ugpu_scanner* s, bool sparse)
     return e;
   if ((e = s->d_tot.alloc(1)) != hipSuccess || (e = s->d_flags.alloc(1)) != hipSuccess ||
       (e = s->h_tot.alloc(1)) != hipSuccess || (e = s->h_flags.alloc(1)) != hipSuccess ||
+      (e = s->d_rdg.alloc(1)) != hipSuccess || (e = s->h_rdg.alloc(1)) != hipSuccess ||
       (e = hipEventCreate(&s->ev0)) != hipSuccess || (e = hipEventCreate(&s->ev1)) != hipSuccess)
     return e;
   return hipSuccess;
@@ -965,8 +968,33 @@ int ugpu_scan_kernel_ms(ugpu_scanner* s, float* ms)
   return UGPU_OK;
 }
 
+namespace {
+int scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint32_t* d_cap, uint64_t capacity, void* stream);
+}
+
 int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint32_t* d_cap, uint64_t capacity,
                       void* stream)
+{
+  const int rc = scan_offsets(s, d_start, d_len, d_cap, capacity, stream);
+  if (rc != UGPU_OK) return rc;
+  // A record's length is 32 bits.  Where the chain had 2^32 bytes or more to
+  // read, a match may be longer: the digest of the totals (64-bit lengths)
+  // then differs from the digest of the written records by a multiple of 2^32
+  // below 2^64 (the lengths add up to at most the bytes read).  No record of
+  // such a scan is handed out.
+  const uint64_t n = s->h_tot->count;
+  if (s->last_args[2] - s->last_args[0] < (1ull << 32) || n == 0 || !d_len) return UGPU_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  HIP_TRY(launch_record_digest(d_start, d_len, n, s->d_rdg, st));
+  HIP_TRY(hipMemcpyAsync(s->h_rdg, s->d_rdg, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (*s->h_rdg != s->h_tot->digest)
+    return fail(UGPU_UNSUPPORTED, "a match of 2^32 bytes or more: its length does not fit a record");
+  return UGPU_OK;
+}
+
+namespace {
+int scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint32_t* d_cap, uint64_t capacity, void* stream)
 {
   if (!s || !s->have_scan) return fail(UGPU_INVAL, "no scan issued");
   if (!d_cap && (s->dfa->t.cap1 == 0 || s->dfa->t.anchored))
@@ -1057,6 +1085,7 @@ int ugpu_scan_offsets(ugpu_scanner* s, uint64_t* d_start, uint32_t* d_len, uint3
   if (*s->h_flags & UGPU_FLAG_HALO) return fail(UGPU_HALO, "a match walked past the readable end of the shard");
   return UGPU_OK;
 }
+}  // namespace
 
 int ugpu_chain_fix(ugpu_scanner* s, const uint8_t* dbuf, uint64_t lo, uint64_t hi, uint64_t read_end, int at_eof,
                    uint64_t bias, uint64_t old_entry, uint64_t new_entry, ugpu_totals* delta, void* stream)

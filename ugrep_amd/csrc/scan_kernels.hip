@@ -596,7 +596,29 @@ __global__ void pack_records_kernel(const uint64_t* start, const uint32_t* len, 
   }
 }
 
+// sum of 31 * start + len over n written records (ugpu_totals' digest, taken
+// from the 32-bit record lengths), added to *sum
+__global__ void record_digest_kernel(const uint64_t* start, const uint32_t* len, uint64_t n, uint64_t* sum)
+{
+  uint64_t d = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    d += start[i] * 31 + len[i];
+  for (int o = 32; o; o >>= 1) d += __shfl_down(d, o, 64);
+  if ((threadIdx.x & 63) == 0 && d) atomicAdd((unsigned long long*)sum, (unsigned long long)d);
+}
+
 // ---------------------------------------------------------------- launchers
+hipError_t launch_record_digest(const uint64_t* start, const uint32_t* len, uint64_t n, uint64_t* sum,
+                                hipStream_t stream)
+{
+  hipError_t e = hipMemsetAsync(sum, 0, sizeof(uint64_t), stream);
+  if (e != hipSuccess || n == 0) return e;
+  const uint64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(record_digest_kernel, dim3((uint32_t)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, stream, start,
+                     len, n, sum);
+  return hipGetLastError();
+}
+
 hipError_t launch_pack_records(const uint64_t* start, const uint32_t* len, const uint32_t* cap, uint64_t n,
                                uint64_t base, uint8_t* out, int caps, int dense, uint64_t* esc, uint32_t* nesc,
                                hipStream_t stream)

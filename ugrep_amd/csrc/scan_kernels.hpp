@@ -282,6 +282,9 @@ hipError_t launch_gen(int kind, uint64_t seed, uint64_t off, uint8_t* dbuf, uint
 // sparse (prefiltered) wave-persistent kernel, sparse_kernel.hip
 hipError_t launch_sparse(const ScanParams& P, bool write, size_t smem, hipStream_t stream);
 hipError_t launch_stage_copy(const ScanParams& P, hipStream_t stream);
+// *sum = the digest (sum of 31 * start + len) of n written records
+hipError_t launch_record_digest(const uint64_t* start, const uint32_t* len, uint64_t n, uint64_t* sum,
+                                hipStream_t stream);
 hipError_t sparse_occupancy(const ScanParams& P, size_t smem, int* blocks_per_cu);
 size_t sparse_smem_bytes(uint32_t ntrans_pad, uint32_t nstates, uint32_t nlds_acap = 0);
 // context tables whose acap (+ amap) entries sparse_kernel stages in LDS
