@@ -428,6 +428,31 @@ int ugpu_stream_reserve(const ugpu_dfa *dfa, int n, uint64_t feed_bytes);
 int ugpu_lines(const uint8_t *dbuf, uint64_t len, const uint64_t *d_start, uint64_t n, uint64_t *d_line,
                uint64_t *newlines, uint64_t *matching_lines, void *stream);
 
+/* Column, line begin and line of byte positions: the -k and -n of ugrep -onkb
+   (-b is the position itself).  Same buffer rules as ugpu_lines.  d_pos is an
+   ascending device list of n positions in [0, len] (repeats allowed), e.g. the
+   match starts, or the ascending list of start + len for the match ends.  For
+   a position p:
+     d_bol[i]  = 1 + the offset of the last '\n' in [0, p), or 0 when there is
+                 none (matcher->bol(); p - d_bol[i] is AbstractMatcher::border(),
+                 absmatcher.h:1153-1157); a position on a '\n' belongs to the
+                 line that newline ends, as in ugpu_select_lines;
+     d_line[i] = 1 + the number of '\n' in [0, p): the d_line of ugpu_lines;
+     d_col[i]  = AbstractMatcher::columno() (absmatcher.h:795-816), 0-based
+                 (ugrep prints d_col + 1): the value of k after the fold over
+                 the bytes [d_bol[i], p) from 0 in which a '\t' does
+                 k += 1 + (~k & (tab - 1)) and any other byte
+                 k += ((byte & 0xC0) != 0x80), so UTF-8 continuation bytes
+                 count 0 and every other byte 1 ('\r', NUL and invalid UTF-8
+                 included).
+   tab is ugrep's --tabs=NUM (src/ugrep.cpp:6689-6691, default 8): 1, 2, 4 or
+   8, anything else is UGPU_INVAL.  Each of the three arrays may be NULL, all
+   three NULL is UGPU_INVAL (both are decided before the device is touched).
+   A position > len gets UINT64_MAX in every output.  n == 0 and len == 0 are
+   valid.  Synchronous. */
+int ugpu_columns(const uint8_t *dbuf, uint64_t len, const uint64_t *d_pos, uint64_t n, uint32_t tab,
+                 uint64_t *d_col, uint64_t *d_bol, uint64_t *d_line, void *stream);
+
 /* --- line records (the bol/eol half) ---
    Same buffer rules as ugpu_lines.  Line k (1-based) is the bytes after the
    (k-1)-th '\n' up to and including the k-th; a non-empty tail after the last

@@ -24,6 +24,14 @@ every list; per step one count-only call and one call that writes the records.
 In the same run it times the K count-only ugpu_select_lines calls a caller
 needs without the fused pass (one per list; the K line lists would still have
 to be copied and combined on the host, which is not timed).
+
+--columns times ugpu_columns on the match starts: per step one
+ugpu_columns call with all three outputs and one ugpu_lines call on the same
+list, alternating, each timed on its own; then the same with ugpu_lines held to
+its dense assign pass (UGPU_LINES_MODE=1), the pass ugpu_columns' assign pass
+corresponds to.  Algorithmic bytes of ugpu_columns: the buffer twice plus 8 B
+read and 24 B written per position.  A kernel trace of the run gives
+col_summary_kernel / col_assign_kernel beside nl_count_kernel / nl_assign_kernel.
 """
 import argparse
 import json
@@ -50,6 +58,8 @@ def main():
     ap.add_argument("--select", action="store_true", help="time ugpu_select_lines instead of ugpu_lines")
     ap.add_argument("--bool", type=int, default=0, metavar="K", dest="nbool",
                     help="time ugpu_select_lines_bool over K match lists (1..16)")
+    ap.add_argument("--columns", action="store_true", help="time ugpu_columns beside ugpu_lines")
+    ap.add_argument("--tab", type=int, default=8, help="--columns: the tab size")
     ap.add_argument("--out", default="", help="also write the JSON line to this file")
     args = ap.parse_args()
     pkey, kind, size = CONFIGS[args.config]
@@ -76,6 +86,8 @@ def main():
     if args.select:
         return select(args, dev, sptr, buf, n, starts, lens, m)
     del lens
+    if args.columns:
+        return columns(args, dev, sptr, buf, n, starts, m)
     lines = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
     torch.cuda.synchronize(dev)
     for _ in range(args.warmup):
@@ -144,6 +156,50 @@ def select(args, dev, sptr, buf, n, starts, lens, m):
         "ms_inverted_count_call": round(t_inv * 1e3, 4), "ms_ugpu_lines_count_call": round(t_lines * 1e3, 4),
         "GBps_input_write_call": round(n / t_write / 1e9, 1),
         "GBps_algorithmic_write_call": round(alg / t_write / 1e9, 1), "algorithmic_bytes": alg}), flush=True)
+
+
+def columns(args, dev, sptr, buf, n, starts, m):
+    bp, sp = buf.data_ptr(), starts.data_ptr()
+    out = torch.empty((3, max(m, 1)), dtype=torch.int64, device=dev)
+    lines = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+
+    def alternate():
+        """(s per ugpu_columns call, s per ugpu_lines call), one of each per step"""
+        tc = tl = 0.0
+        for i in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            ugrep_amd.columns(bp, n, sp, m, args.tab, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), sptr)
+            t1 = time.perf_counter()
+            ugrep_amd.lines(bp, n, sp, m, lines.data_ptr(), sptr)
+            t2 = time.perf_counter()
+            if i >= args.warmup:
+                tc, tl = tc + t1 - t0, tl + t2 - t1
+        return tc / args.steps, tl / args.steps
+
+    t_col, t_lines = alternate()
+    os.environ["UGPU_LINES_MODE"] = "1"
+    t_col2, t_dense = alternate()
+    del os.environ["UGPU_LINES_MODE"]
+    # sanity (not timed): the lines are ugpu_lines', a line begins behind a newline, the column is within the line
+    col, bol, line = out[0, :m], out[1, :m], out[2, :m]
+    st = starts[:m]
+    ok = bool((line == lines[:m]).all().item()) and bool(((bol == 0) | (buf[(bol - 1).clamp(min=0)] == 10)).all().item()) \
+        and bool(((bol <= st) & (col >= 0) & (col <= (st - bol) * args.tab)).all().item())
+    alg = 2 * n + 32 * m  # the buffer twice + a position read and three values written per position
+    res = {
+        "what": "ugpu_columns (column, line begin and line of every match start) beside ugpu_lines, alternating",
+        "config": args.config, "bytes": n, "positions": m, "tab": args.tab, "outputs_ok": ok,
+        "ms_columns_call": round(t_col * 1e3, 4), "ms_lines_call": round(t_lines * 1e3, 4),
+        "ms_columns_call_2": round(t_col2 * 1e3, 4), "ms_lines_dense_call": round(t_dense * 1e3, 4),
+        "GBps_input_columns_call": round(n / t_col / 1e9, 1),
+        "GBps_algorithmic_columns_call": round(alg / t_col / 1e9, 1), "algorithmic_bytes": alg,
+        "max_column": int(col.max().item()) if m else 0}
+    text = json.dumps(res)
+    print(text, flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
 
 
 NEEDLES = ["qux|zot|wib", "mep|dak|yol", "vug|hix|pym", "kob|raz|tew", "jid|nuf|gax", "lev|sop|cuz", "wam|biq|fyr",

@@ -9,10 +9,12 @@ from ._lib import (GEN_CODE, GEN_PLANTED, GEN_UTF8, GEN_WORDS, MODE_COUNT, MODE_
 from .matcher import (compile_regex, Matcher, Pattern, Records, Scanner, Stream, check_utf8, find_all, find_all_multi, find_nul, gen,  # noqa: F401
                       host_plan, host_prefilter, host_tables, host_transducer, is_binary, isutf8, lines,
                       LineResult, context_lines, grep_lines, line_spans, select_lines,
+                      PositionResult, columns, find_positions,
                       grep_bool, host_newline, host_ngram, host_ngram_candidates, parse_bool_query, select_lines_bool,
                       BatchResult, find_batch, host_batch_plan, split_matches)
 
 __all__ = ["compile_regex", "Pattern", "Matcher", "Records", "Scanner", "Stream", "find_all", "find_all_multi", "gen", "host_tables", "host_plan", "host_prefilter", "Unsupported",
            "UgpuError", "lines", "isutf8", "check_utf8", "find_nul", "is_binary", "select_lines", "line_spans", "context_lines",
            "grep_lines", "LineResult", "select_lines_bool", "parse_bool_query", "grep_bool", "host_newline",
-           "host_ngram", "host_ngram_candidates", "BatchResult", "find_batch", "host_batch_plan", "split_matches"]
+           "host_ngram", "host_ngram_candidates", "BatchResult", "find_batch", "host_batch_plan", "split_matches",
+           "columns", "find_positions", "PositionResult"]

@@ -151,6 +151,7 @@ def _load():
         "ugpu_stream_reserve": (ctypes.c_int, [V, ctypes.c_int, ctypes.c_uint64]),
         "ugpu_lines": (ctypes.c_int, [V, ctypes.c_uint64, V, ctypes.c_uint64, V, P(ctypes.c_uint64),
                                       P(ctypes.c_uint64), V]),
+        "ugpu_columns": (ctypes.c_int, [V, ctypes.c_uint64, V, ctypes.c_uint64, ctypes.c_uint32, V, V, V, V]),
         "ugpu_select_lines": (ctypes.c_int, [V, ctypes.c_uint64, V, V, ctypes.c_uint64, ctypes.c_uint32, V, V, V,
                                              ctypes.c_uint64, P(ctypes.c_uint64), P(ctypes.c_uint64), V]),
         "ugpu_line_spans": (ctypes.c_int, [V, ctypes.c_uint64, V, ctypes.c_uint64, V, V, V]),

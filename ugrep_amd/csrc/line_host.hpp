@@ -89,6 +89,29 @@ inline hipError_t newline_prefix(WaveWs& ws, const LinesParams& L, bool sparse, 
   return newline_prefix(ws, L, sparse, 1, [] { return hipSuccess; }, st, newlines);
 }
 
+// The stitch of ugpu_columns.  out: the summary pass's four per-range arrays
+// (newlines, 1 + last newline, column function a | kind << 32, b: ColParams);
+// in: what holds at each range's first byte (newlines before it, begin of its
+// line, its column).  A line may run through many ranges, and one of 4 GiB or
+// more has columns past 2^32: everything is 64 bits here.
+inline void column_stitch(const uint64_t* out, uint64_t* in, uint64_t nw, uint32_t tmask)
+{
+  uint64_t newlines = 0, bol = 0, k = 0;
+  for (uint64_t i = 0; i < nw; ++i) {
+    in[i] = newlines;
+    in[nw + i] = bol;
+    in[2 * nw + i] = k;
+    newlines += out[i];
+    if (out[nw + i]) bol = out[nw + i];
+    const uint64_t a = out[2 * nw + i] & 0xffffffffu, b = out[3 * nw + i];
+    switch ((uint32_t)(out[2 * nw + i] >> 32)) {
+      case kColAdd: k += a; break;
+      case kColTab: k = ((k + a) | tmask) + 1 + b; break;
+      default: k = a; break;
+    }
+  }
+}
+
 inline LinesParams line_ranges_params(const uint8_t* g, uint64_t len, uint64_t per, uint64_t nw)
 {
   LinesParams L{};

@@ -350,6 +350,36 @@ struct SpanParams {
 hipError_t launch_sel_summary(const SelParams& S, hipStream_t stream);
 hipError_t launch_sel(const SelParams& S, bool write, hipStream_t stream);
 hipError_t launch_spans(const SpanParams& Q, hipStream_t stream);
+// column numbers, columns.hip: the same wave ranges.  A byte range maps the
+// column k at its first byte to the column behind its last byte as one of
+//   kColAdd:   k + a                         (no tab, no newline)
+//   kColTab:   ((k + a) | (T - 1)) + 1 + b   (a: columns before its first tab, b: after it)
+//   kColConst: a                             (it holds a '\n': the column behind its last one)
+// Within a range a and b fit 32 bits (a range of 8-column tabs: per < 512 MiB).
+constexpr uint32_t kColAdd = 0, kColTab = 1, kColConst = 2;
+struct ColParams {
+  const uint8_t* g;         // 16-byte aligned buffer
+  uint64_t len;             // bytes
+  uint64_t per;             // bytes per wave range (multiple of 4 KiB)
+  uint64_t nwaves;
+  uint32_t tmask;           // tab size - 1
+  const uint64_t* pos;      // ascending positions (<= len; larger ones get UINT64_MAX)
+  uint64_t npos;
+  // out (summary pass), per wave range
+  uint64_t* counts;         // newlines
+  uint64_t* lastnl;         // 1 + position of the range's last '\n' (0: none)
+  uint64_t* fn_a;           // the range's column function: a | kind << 32
+  uint64_t* fn_b;           // b
+  // in (assign pass): what holds at each range's first byte
+  const uint64_t* prefix;   // newlines before it
+  const uint64_t* bol;      // begin of its line
+  const uint64_t* kin;      // its column
+  uint64_t* col;            // out, each may be NULL
+  uint64_t* bolout;
+  uint64_t* line;
+};
+hipError_t launch_col_summary(const ColParams& C, hipStream_t stream);
+hipError_t launch_col_assign(const ColParams& C, hipStream_t stream);
 // Boolean line queries, linebool.hip: SelParams for up to 16 match lists and a
 // CNF over them.  The host passes only the lists the formula uses, renumbered
 // from 0, so bit t of a clause mask is list t of these arrays.

@@ -558,6 +558,41 @@ def lines(dptr, length, d_start=0, n=0, d_line=0, stream=0):
     return nl.value, ml.value
 
 
+def columns(dptr, length, d_pos, n, tab=8, d_col=0, d_bol=0, d_line=0, stream=0):
+    """ugpu_columns over a 16-byte aligned device buffer and an ascending device
+    list of n positions in [0, length]: fills d_col[i] with the 0-based column
+    of d_pos[i] (ugrep -k prints it plus 1; `tab` is --tabs: 1, 2, 4 or 8),
+    d_bol[i] with the begin of its line and d_line[i] with its 1-based line.
+    Each output may be 0, not all three."""
+    check(lib.ugpu_columns(ctypes.c_void_p(dptr), length, ctypes.c_void_p(d_pos or None), n, tab,
+                           ctypes.c_void_p(d_col or None), ctypes.c_void_p(d_bol or None),
+                           ctypes.c_void_p(d_line or None), ctypes.c_void_p(stream)))
+
+
+PositionResult = collections.namedtuple("PositionResult", "line column start length cap")
+
+
+def find_positions(pattern, data, tab=8):
+    """The rows of `ugrep -onkb --tabs=tab` for one input:
+    PositionResult(line, column, start, length, cap) numpy arrays, one entry
+    per match; line is 1-based, column 0-based (ugrep prints column + 1), start
+    the byte offset.  Composes find_all and columns; the column work runs on
+    the current device."""
+    import torch
+    ptr, n, keep = _buffer_ptr(data)
+    dev = _device_input(ptr, n, keep)
+    r = find_all(pattern, dev[:n], offsets=True)
+    m = int(r.count)
+    out = torch.zeros((2, max(m, 1)), dtype=torch.int64, device=dev.device)
+    if m:
+        d_pos = torch.from_numpy(r.start.astype(np.int64)).to(dev.device)
+        torch.cuda.synchronize()
+        columns(dev.data_ptr(), n, d_pos.data_ptr(), m, tab, d_col=out[0].data_ptr(), d_line=out[1].data_ptr())
+    col, line = (a.astype(np.uint64) for a in out[:, :m].cpu().numpy())
+    del keep
+    return PositionResult(line, col, r.start, r.length, r.cap)
+
+
 def select_lines(dptr, length, d_start, d_len, n, invert=False, d_begin=0, d_end=0, d_lineno=0, capacity=0,
                  stream=0):
     """ugpu_select_lines over a 16-byte aligned device buffer and its sorted
