@@ -638,6 +638,75 @@ int ugpu_find_nul(const uint8_t *dbuf, uint64_t len, uint64_t *pos, void *stream
 #define UGPU_BIN_INIT_WINDOW 4u
 int ugpu_is_binary(const uint8_t *dbuf, uint64_t len, uint32_t flags, int *binary, void *stream);
 
+/* --- input encodings ---
+   The conversion reflex::Input does in front of the matcher: UTF-16/32,
+   Latin-1, the 8-bit code pages and --null-data into the UTF-8 (or swapped)
+   bytes every scan and line consumer takes.  The result is, byte for byte,
+   what Input::file_get (lib/input.cpp:748-1023) writes for one call with an
+   unbounded n.  Its behaviour when a multi-byte sequence straddles the end of
+   the caller's buffer (uidx_/ulen_, :790-797) depends on chunk sizes and has
+   no counterpart.  Not reproduced either: the buffered head bytes when
+   --encoding=UTF-16/32 is forced on a file without a BOM (:1307-1394), where
+   the reference reads stale bytes. */
+#define UGPU_ENC_PLAIN 0 /* also what ugpu_detect_bom returns for "no BOM" */
+#define UGPU_ENC_UTF8 1
+#define UGPU_ENC_UTF16BE 2
+#define UGPU_ENC_UTF16LE 3
+#define UGPU_ENC_UTF32BE 4
+#define UGPU_ENC_UTF32LE 5
+#define UGPU_ENC_LATIN1 6
+#define UGPU_ENC_PAGE 7
+#define UGPU_ENC_NULL_DATA 8
+
+/* Input::file_init (lib/input.cpp:661-745), host only: the encoding a BOM in
+   head[0, min(len, 4)) announces and the bytes to skip; len is the length of
+   the whole input (head holds its first min(len, 4) bytes).
+     EF BB BF                      UTF8, skip 3
+     FE FF                         UTF16BE, skip 2
+     FF FE 00 00                   UTF32LE, skip 4
+     FF FE, len >= 4               UTF16LE, skip 2 (the reference converts the
+                                   first unit inside file_init, :706-723, by
+                                   the rules of the body)
+     FF FE, len < 4                PLAIN, skip 0
+     00 00 FE FF                   UTF32BE, skip 4
+     anything else                 PLAIN, skip 0 */
+int ugpu_detect_bom(const uint8_t *head, uint64_t len, uint32_t *enc, uint32_t *skip);
+
+/* Host only: *bound = the largest output of `bytes` input bytes under enc
+   (UTF-16: 5 bytes per 2; UTF-32: 5 per 4; Latin-1: 2 per 1; a code page: 3
+   per 1; null data: 1 per 1).  UGPU_INVAL for PLAIN, UTF8 and unknown enc. */
+int ugpu_transcode_bound(uint32_t enc, uint64_t bytes, uint64_t *bound);
+
+/* Converts dbuf[start, len) (a device buffer, 16-byte aligned with a readable
+   last granule as for ugpu_lines; start skips a BOM without breaking that
+   alignment) into d_dst[0, *out_len) (device, 16-byte aligned, capacity
+   bytes).  With utf8(c) = reflex::utf8(int, char*) (include/reflex/utf8.h:
+   76-135: 1-4 bytes by the usual ranges, D800..DFFF not rejected (3 bytes),
+   c > 0x10FFFF the five bytes F8 88 80 80 80 of REFLEX_NONCHAR):
+     UTF16BE/LE (:770-847)  units u[0, floor(n / 2)), a trailing odd byte is
+        dropped.  A unit in D800..DBFF (H) always consumes the unit behind it:
+        it emits utf8(0x10000 + ((u[i] - 0xD800) << 10) + (u[i+1] - 0xDC00))
+        when that unit exists and lies in DC00..DFFF, NONCHAR otherwise, and
+        the consumed unit emits nothing whatever it is.  A unit in DC00..DFFF
+        that is not consumed emits NONCHAR; any other unit emits utf8(u[i]).
+     UTF32BE/LE (:848-909)  per 4 bytes, c a signed 32-bit int: c < 0x80
+        (negative values included) emits the byte c & 0xFF, otherwise utf8(c);
+        a trailing 1-3 bytes are dropped.
+     LATIN1 (:910-938)      a byte < 0x80 unchanged, otherwise utf8(byte).
+     PAGE (:939-1000)       c = page[byte], the 256-entry table
+        Input::file_encoding(enc, page) receives (host memory): c < 0x80 one
+        byte, otherwise utf8(c).
+     NULL_DATA (:1001-1016) '\0' and '\n' swapped.
+   d_dst NULL is a size query: the summary pass only, *out_len valid.  When
+   *out_len > capacity the call returns UGPU_CAPACITY with *out_len valid and
+   nothing written; otherwise only d_dst[0, *out_len) is written.  UGPU_INVAL,
+   decided before the device is touched: an unknown enc, PLAIN or UTF8 (nothing
+   to convert), PAGE without a page or a page with another enc, start > len.
+   len == start is valid and gives 0.  Offsets are 64-bit throughout (a 2.2 GiB
+   Latin-1 input gives more than 4 GiB).  Synchronous. */
+int ugpu_transcode(const uint8_t *dbuf, uint64_t len, uint64_t start, uint32_t enc, const uint16_t *page,
+                   uint8_t *d_dst, uint64_t capacity, uint64_t *out_len, void *stream);
+
 /* --- synthetic corpora, generated on device --- */
 #define UGPU_GEN_WORDS 1
 #define UGPU_GEN_PLANTED 2

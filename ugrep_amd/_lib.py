@@ -34,6 +34,8 @@ BOOL_FILES = 2
 BOOL_MAX_LISTS, BOOL_MAX_CLAUSES = 16, 64
 BATCH_ONE_SCAN = 1
 
+ENC_PLAIN, ENC_UTF8, ENC_UTF16BE, ENC_UTF16LE, ENC_UTF32BE, ENC_UTF32LE, ENC_LATIN1, ENC_PAGE, ENC_NULL_DATA = range(9)
+
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
 c_u16p = ctypes.POINTER(ctypes.c_uint16)
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
@@ -168,6 +170,10 @@ def _load():
         "ugpu_check_utf8": (ctypes.c_int, [V, ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_find_nul": (ctypes.c_int, [V, ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_is_binary": (ctypes.c_int, [V, ctypes.c_uint64, ctypes.c_uint32, P(ctypes.c_int), V]),
+        "ugpu_detect_bom": (ctypes.c_int, [c_u8p, ctypes.c_uint64, P(ctypes.c_uint32), P(ctypes.c_uint32)]),
+        "ugpu_transcode_bound": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint64, P(ctypes.c_uint64)]),
+        "ugpu_transcode": (ctypes.c_int, [V, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_u16p, V,
+                                          ctypes.c_uint64, P(ctypes.c_uint64), V]),
         "ugpu_compile": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(c_u32p),
                                         P(ctypes.c_uint32)]),
         "ugpu_opc_free": (None, [c_u32p]),

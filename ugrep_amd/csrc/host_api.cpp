@@ -666,4 +666,40 @@ int ugpu_tables_equivalent_host(const uint32_t* opc_a, uint32_t nop_a, const uin
   return UGPU_OK;
 }
 
+// Input::file_init's BOM checks (lib/input.cpp:661-745) on the first bytes
+int ugpu_detect_bom(const uint8_t* head, uint64_t len, uint32_t* enc, uint32_t* skip)
+{
+  if (!enc || !skip || (len && !head)) return fail(UGPU_INVAL, "NULL argument");
+  const uint8_t b0 = len > 0 ? head[0] : 1, b1 = len > 1 ? head[1] : 1, b2 = len > 2 ? head[2] : 1,
+                b3 = len > 3 ? head[3] : 1;  // (1 takes part in no BOM)
+  *enc = UGPU_ENC_PLAIN, *skip = 0;
+  if (len >= 4 && b0 == 0 && b1 == 0 && b2 == 0xFE && b3 == 0xFF)
+    *enc = UGPU_ENC_UTF32BE, *skip = 4;
+  else if (len >= 2 && b0 == 0xFE && b1 == 0xFF)
+    *enc = UGPU_ENC_UTF16BE, *skip = 2;
+  else if (len >= 4 && b0 == 0xFF && b1 == 0xFE && b2 == 0 && b3 == 0)
+    *enc = UGPU_ENC_UTF32LE, *skip = 4;
+  else if (len >= 4 && b0 == 0xFF && b1 == 0xFE)
+    *enc = UGPU_ENC_UTF16LE, *skip = 2;
+  else if (len >= 3 && b0 == 0xEF && b1 == 0xBB && b2 == 0xBF)
+    *enc = UGPU_ENC_UTF8, *skip = 3;
+  return UGPU_OK;
+}
+
+int ugpu_transcode_bound(uint32_t enc, uint64_t bytes, uint64_t* bound)
+{
+  if (!bound) return fail(UGPU_INVAL, "NULL argument");
+  switch (enc) {
+    case UGPU_ENC_UTF16BE:
+    case UGPU_ENC_UTF16LE: *bound = bytes / 2 * 5; break;  // a lone low surrogate: NONCHAR
+    case UGPU_ENC_UTF32BE:
+    case UGPU_ENC_UTF32LE: *bound = bytes / 4 * 5; break;  // a value past 0x10FFFF: NONCHAR
+    case UGPU_ENC_LATIN1: *bound = bytes * 2; break;
+    case UGPU_ENC_PAGE: *bound = bytes * 3; break;
+    case UGPU_ENC_NULL_DATA: *bound = bytes; break;
+    default: return fail(UGPU_INVAL, "no conversion for this encoding");
+  }
+  return UGPU_OK;
+}
+
 }  // extern "C"

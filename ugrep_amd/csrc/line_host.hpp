@@ -112,6 +112,23 @@ inline void column_stitch(const uint64_t* out, uint64_t* in, uint64_t nw, uint32
   }
 }
 
+// The stitch of ugpu_transcode.  out: the summary pass's three per-range arrays
+// (output bytes for the incoming bit 0, for the incoming bit 1, the range
+// function: TcParams; without `carry` only the first is read); in: each
+// range's exclusive output offset and its incoming bit.  Returns the output
+// length; an output passes 4 GiB from 2 GiB of Latin-1.
+inline uint64_t transcode_stitch(const uint64_t* out, uint64_t* in, uint64_t nw, bool carry)
+{
+  uint64_t off = 0, c = 0;
+  for (uint64_t i = 0; i < nw; ++i) {
+    in[i] = off;
+    in[nw + i] = c;
+    off += out[(c ? nw : 0) + i];
+    if (carry) c = (out[2 * nw + i] >> c) & 1u;
+  }
+  return off;
+}
+
 inline LinesParams line_ranges_params(const uint8_t* g, uint64_t len, uint64_t per, uint64_t nw)
 {
   LinesParams L{};

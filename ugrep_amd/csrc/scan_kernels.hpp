@@ -380,6 +380,34 @@ struct ColParams {
 };
 hipError_t launch_col_summary(const ColParams& C, hipStream_t stream);
 hipError_t launch_col_assign(const ColParams& C, hipStream_t stream);
+// input encodings, transcode.hip: the same wave ranges over the n bytes to
+// convert, counted from `start` (range offsets are offsets from there).  A
+// UTF-16 range maps the bit "its first unit is consumed by the high surrogate
+// before it" to the same bit of the unit behind it, and its output length
+// depends on that bit: a range function is two bits (bit c: the outgoing bit
+// for the incoming bit c; 2 is the identity) and two counts.
+struct TcParams {
+  const uint8_t* g;         // buffer + (start & ~3): dword aligned
+  uint32_t shift;           // start & 3: byte j to convert is g[shift + j]
+  uint32_t enc;             // UGPU_ENC_*
+  uint64_t n;               // bytes to convert
+  uint64_t readable;        // bytes readable from g (to the end of the buffer's last granule)
+  uint64_t per;             // bytes per wave range (multiple of 4 KiB)
+  uint64_t nwaves;
+  // out (summary pass), per wave range
+  uint64_t* cnt0;           // output bytes (UTF-16: for the incoming bit 0)
+  uint64_t* cnt1;           // UTF-16: output bytes for the incoming bit 1
+  uint64_t* fn;             // UTF-16: the range function
+  // in (write pass): what holds at each range's first byte
+  const uint64_t* obase;    // output offset
+  const uint64_t* cin;      // UTF-16: the incoming bit
+  uint8_t* dst;             // 16-byte aligned
+};
+struct TcPage {
+  uint16_t v[256];          // UGPU_ENC_PAGE: the code page
+};
+hipError_t launch_tc_summary(const TcParams& P, const TcPage& page, hipStream_t stream);
+hipError_t launch_tc_write(const TcParams& P, const TcPage& page, hipStream_t stream);
 // Boolean line queries, linebool.hip: SelParams for up to 16 match lists and a
 // CNF over them.  The host passes only the lists the formula uses, renumbered
 // from 0, so bit t of a clause mask is list t of these arrays.

@@ -1135,3 +1135,93 @@ def is_binary(dptr, length, null_data=False, nul_only=False, init_window=False, 
 def gen(kind, seed, off, dptr, length, stream=0):
     """Generate corpus bytes [off, off+length) on the device (ugpu_gen)."""
     check(lib.ugpu_gen(kind, seed, off, ctypes.c_void_p(dptr), length, ctypes.c_void_p(stream)))
+
+
+# ---- input encodings (ugpu_detect_bom, ugpu_transcode)
+
+# the names of ugrep's --encoding= that have no code page (src/ugrep.cpp:4497-4541), lower case
+ENCODINGS = {"utf-8": _lib.ENC_UTF8, "utf-16be": _lib.ENC_UTF16BE, "utf-16le": _lib.ENC_UTF16LE, "utf-16": _lib.ENC_UTF16BE,
+             "utf-32be": _lib.ENC_UTF32BE, "utf-32le": _lib.ENC_UTF32LE, "utf-32": _lib.ENC_UTF32BE,
+             "latin1": _lib.ENC_LATIN1, "iso-8859-1": _lib.ENC_LATIN1, "null-data": _lib.ENC_NULL_DATA}
+
+
+def detect_bom(head, length=None):
+    """Input::file_init's BOM checks (ugpu_detect_bom): (enc, skip) for an
+    input of `length` bytes (default: len(head)) whose first bytes are `head`."""
+    head = bytes(head[:4])
+    n = len(head) if length is None else int(length)
+    buf = (ctypes.c_uint8 * 4)(*head[:min(n, 4)])
+    enc, skip = ctypes.c_uint32(), ctypes.c_uint32()
+    check(lib.ugpu_detect_bom(buf, n, ctypes.byref(enc), ctypes.byref(skip)))
+    return enc.value, skip.value
+
+
+def transcode_bound(enc, nbytes):
+    """ugpu_transcode_bound: the largest output of nbytes input bytes under enc."""
+    b = ctypes.c_uint64()
+    check(lib.ugpu_transcode_bound(enc, nbytes, ctypes.byref(b)))
+    return b.value
+
+
+def transcode(dptr, length, enc, start=0, page=None, d_dst=0, capacity=0, stream=0):
+    """ugpu_transcode: converts the device bytes [start, length) of a 16-byte
+    aligned buffer from `enc` (a _lib.ENC_* value; `page`: the 256 values of a
+    code page for ENC_PAGE) into the 16-byte aligned device buffer d_dst of
+    `capacity` bytes and returns the output length; d_dst 0 only asks for that
+    length.  Too small a capacity raises UgpuError with code UGPU_CAPACITY and
+    the length in its .out_len; nothing is written then."""
+    out = ctypes.c_uint64()
+    pg = None if page is None else (ctypes.c_uint16 * 256)(*[int(x) for x in page])
+    rc = lib.ugpu_transcode(ctypes.c_void_p(dptr), length, start, enc, pg, ctypes.c_void_p(d_dst or None), capacity,
+                            ctypes.byref(out), ctypes.c_void_p(stream))
+    if rc == _lib.UGPU_CAPACITY:
+        err = _lib.UgpuError(rc, lib.ugpu_last_error().decode(errors="replace"))
+        err.out_len = out.value
+        raise err
+    check(rc)
+    return out.value
+
+
+def decode_input(data, encoding=None, page=None):
+    """Host bytes as the UTF-8 (or plain) device bytes the scans and line
+    consumers take, as reflex::Input hands them to the matcher: (device uint8
+    tensor, n).  The tensor is 16-byte aligned and holds a zeroed granule
+    behind its n bytes.  Without `encoding` the BOM decides (detect_bom; none:
+    the bytes as they are); `encoding` is a name of ENCODINGS or an ENC_* value,
+    and a `page` (256 values) selects ENC_PAGE.  A BOM is skipped only when it
+    was detected, not under a given encoding."""
+    import torch
+    _, n, keep = _buffer_ptr(data)
+    host = keep if isinstance(keep, np.ndarray) else keep.view(torch.uint8).reshape(-1).cpu().numpy()
+    skip = 0
+    if page is not None:
+        enc = _lib.ENC_PAGE
+    elif encoding is None:
+        enc, skip = detect_bom(host[:4].tobytes() if n else b"", n)
+    else:
+        enc = ENCODINGS[encoding.lower()] if isinstance(encoding, str) else int(encoding)
+    if enc in (_lib.ENC_PLAIN, _lib.ENC_UTF8):
+        dev = torch.zeros(n - skip + 16, dtype=torch.uint8, device="cuda")
+        if n - skip:
+            dev[:n - skip].copy_(torch.from_numpy(host[skip:].copy()))
+        del keep
+        return dev, n - skip
+    src = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+    if n:
+        src[:n].copy_(torch.from_numpy(host.copy()))
+    torch.cuda.synchronize()
+    m = transcode(src.data_ptr(), n, enc, skip, page)
+    dst = torch.zeros(m + 16, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    got = transcode(src.data_ptr(), n, enc, skip, page, dst.data_ptr(), m)
+    assert got == m
+    del keep
+    return dst, m
+
+
+def find_encoded(pattern, data, encoding=None, page=None, offsets=True):
+    """find_all over decode_input(data, encoding, page): the matches of an
+    input in another encoding; the offsets are positions in the converted
+    stream, as ugrep -b prints them."""
+    dev, n = decode_input(data, encoding, page)
+    return find_all(pattern, dev[:n], offsets=offsets)
