@@ -8,7 +8,7 @@ that outgrows its 32-byte window is continued by the whole wave (coop_walk),
 stops at its wave's range end (an open walk), and fix_kernel resolves open
 walks from the next waves' records; waves a match covers are skipped in one
 step.  Parity against the oracle (record by record where the lists are
-small), the forest fallback when an open walk cannot be resolved, OFFSETS,
+small), an open walk that only a whole wave can resolve, OFFSETS,
 and wall-time bounds on the runs of the round-3 verdict (1, 16 and 64 MiB
 runs of `a` in a 256 MiB buffer, >= 100 GB/s)."""
 import time
@@ -102,10 +102,12 @@ def test_open_walk_ends_early(U):
     _check(U, "a[^\n]*b", host)
 
 
-def test_unresolved_open_walk_goes_to_the_forest(U):
+def test_unresolved_open_walk_is_walked_by_one_wave(U):
     """An open walk that neither dies nor meets a later walk within the
     convergence budget (`x[a-z]*y` over 2 MiB of letters without candidates
-    and without `y`): the scan falls back to the forest FIND, still exact."""
+    and without `y`): one wave of fix_kernel walks it to its end (R1b), and
+    the scan does not fall back to the forest FIND (tests/test_open_walks.py
+    has many such walks in one scan)."""
     n = 8 << 20
     host = _filler(n, b"12 ")
     host[1 << 20] = ord("x")
@@ -113,7 +115,15 @@ def test_unresolved_open_walk_goes_to_the_forest(U):
     host[5 << 20] = ord("x")
     host[(5 << 20) + 1:(5 << 20) + 9] = ord("z")
     host[(5 << 20) + 9] = ord("y")
-    _check(U, "x[a-z]*y", host)
+    got = _check(U, "x[a-z]*y", host)
+    dev = torch.zeros(n + 16, dtype=torch.uint8, device="cuda")
+    dev[:n].copy_(torch.from_numpy(host))
+    torch.cuda.synchronize()
+    sc = U.Scanner(U.Pattern(U.compile_regex("x[a-z]*y")))
+    sc.scan(dev.data_ptr(), 0, n, n, True, 0, _stream())
+    t = sc.totals()
+    assert (t.count, t.digest, t.dcap) == (got.count, got.digest, got.dcap)
+    assert not t.flags & 8  # UGPU_TOT_FOREST
 
 
 def test_runs_across_shards_and_streams(U):

@@ -22,7 +22,12 @@ namespace ugpu {
 //      wave, 1 KiB a round (coop_continue), until it dies or reaches the end
 //      of the readable bytes (kOpenDead), within kOpenCoopBudget bytes; past
 //      that it gives up (kOpenUnres: UGPU_FLAG_BUDGET, the forest FIND).  The
-//      last open wave of a run of candidate bytes that crosses many waves
+//      threads that find an unresolved walk append its record index to a list
+//      in LDS (at most kOpenCoopMax entries, in no particular order); after a
+//      barrier wave i of the block's 16 takes entries i, i + 16, ...: every
+//      listed walk is walked by exactly one wave, whatever the others have
+//      finished meanwhile.  With more than kOpenCoopMax walks none is taken.
+//      The last open wave of a run of candidate bytes that crosses many waves
 //      (a needle-free letter run under [a-z]+(ing|ed)) is resolved here; the
 //      waves before it converge with their successors in R1.
 //   R2 (wave 0, open waves in descending order, 64 at a time): the ends, each
@@ -189,21 +194,26 @@ __device__ __forceinline__ void resolve_open(const ScanParams& P, const Tab<FMT>
   __syncthreads();
   // R1b: the walks R1 left unresolved, one wave each, when there are few
   {
+    static_assert(kMaxRec <= 65536, "the list of unresolved walks holds 16-bit record indices");
     __shared__ uint32_t nunres;
+    __shared__ uint16_t unres[kOpenCoopMax];
     if (tid == 0) nunres = 0;
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < PER; ++j) {
       const int b = j * kFixThreads + tid;
-      if (b < G && ((openm[b >> 5] >> (b & 31)) & 1u) && P.open[b].type == kOpenUnres) atomicAdd(&nunres, 1u);
+      if (b < G && ((openm[b >> 5] >> (b & 31)) & 1u) && P.open[b].type == kOpenUnres) {
+        const uint32_t slot = atomicAdd(&nunres, 1u);
+        if (slot < (uint32_t)kOpenCoopMax) unres[slot] = (uint16_t)b;
+      }
     }
     __syncthreads();
-    if (nunres && nunres <= (uint32_t)kOpenCoopMax) {
-      for (int b = 0, k = 0; b < G; ++b) {
-        if (!((openm[b >> 5] >> (b & 31)) & 1u)) continue;
-        OpenRec* o = P.open + b;
-        if (o->type != kOpenUnres) continue;
-        if ((k++ % (kFixThreads / 64)) != wid) continue;
+    // (the split comes from the list alone: a walk's type changes under the
+    // waves' hands as they finish, so no wave reads another's between the barriers)
+    const uint32_t nu = nunres;
+    if (nu <= (uint32_t)kOpenCoopMax) {
+      for (uint32_t k = (uint32_t)wid; k < nu; k += kFixThreads / 64) {
+        OpenRec* o = P.open + unres[k];
         uint32_t s = o->sq, lew = o->lew;
         uint64_t q = o->q, lastw = o->lastw;
         const uint64_t lim = q + kOpenCoopBudget < w.rend ? q + kOpenCoopBudget : w.rend;
@@ -356,9 +366,10 @@ __device__ __forceinline__ bool fix_block(const ScanParams& P, const Tab<FMT>& T
       uint32_t le1 = (uint32_t)pad2;
       if (e1 == kOpenEnd) {
         const OpenRec o = P.open[b];
-        e1 = o.e > o.c ? o.e : 0;  // (no match: the chain went on at c1 + 1)
+        // (no match: the chain went on at c1 + 1, so there is no shortcut past
+        // c1; up to c1 the chain is the same whatever became of c1's walk)
+        e1 = o.e > o.c ? o.e : 0;
         le1 = o.le_e;
-        if (e1 == 0) c1 = 0;  // (no shortcut past c1)
       }
       if (r[6] == 0 || nx <= c1) {
         met = done = true;
