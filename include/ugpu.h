@@ -707,6 +707,80 @@ int ugpu_transcode_bound(uint32_t enc, uint64_t bytes, uint64_t *bound);
 int ugpu_transcode(const uint8_t *dbuf, uint64_t len, uint64_t start, uint32_t enc, const uint16_t *page,
                    uint8_t *d_dst, uint64_t capacity, uint64_t *out_len, void *stream);
 
+/* --- file indexes ---
+   The pass ugrep-indexer makes over every file (src/ugrep-indexer.cpp:
+   805-1030) so that ugrep --index can skip files that cannot match.  Per input:
+     table   65536 bytes of 0xff; for every position i and k in 0..7 with
+             i + k < n, bit k of table[h(i, k)] is cleared, h(i, 0) = byte[i],
+             h(i, k) = (61 h(i, k-1) + byte[i+k]) mod 2^16 (indexhash, :806-809;
+             the 64 KiB reads, the 8-byte window and the tail loop of :928-977
+             come to this set of (i, k))
+     fold    size = 65536; while size > 128: z = the zero bits of the AND of
+             the two halves; stop when 100 z >= max_noise * 8 * (size / 2),
+             otherwise that AND is the table and size halves (:997-1027, in
+             float there; z < 2^24 and the divisors are powers of two, so the
+             integer comparison decides the same).  max_noise by accuracy
+             0..9: 80 73 65 57 49 42 34 26 18 10 (noise_percentage, :266-270)
+     binary  over the first min(n, 65536) bytes, the window's last UTF-8
+             sequence cut off first (:892-901), then is_binary (:782-803): a
+             NUL, a lead outside C2..F4 or a lead without its continuation
+             bytes.  This is not reflex::isutf8: surrogates and 3/4-byte
+             overlongs pass.
+   The header byte of an input's record (:1725-1731) is log2(size) | binary << 7;
+   an empty input, and a binary one under UGPU_INDEX_IGNORE_BINARY (-I), has
+   log2 0 and no table.  The bytes to pass are those reflex::Input delivers
+   (ugpu_detect_bom / ugpu_transcode for a file with a BOM).  Archives,
+   decompression, --check, --delete and incremental updates are not here, and
+   neither is the query (Pattern::match_hfa), which reads these tables as the
+   reference's. */
+#define UGPU_INDEX_IGNORE_BINARY 1u
+
+/* The bytes of an input one workgroup hashes: an input of up to this many
+   bytes is hashed, folded and counted in one workgroup, a longer one is cut
+   into chunks of this size whose tables meet in global memory. */
+uint64_t ugpu_index_chunk(void);
+
+/* Indexes the nseg segments [bounds[s], bounds[s+1]) of dbuf[0, len) (a device
+   buffer, 16-byte aligned with a readable last granule as for ugpu_lines;
+   bounds: nseg + 1 ascending host values, bounds[nseg] <= len; segments lie
+   back to back or apart, and no window reads past its segment's end).  Host
+   outputs: header[s] as above, zero_bits[s] the zero bits of the final table
+   (ugrep-indexer -v prints 100 zero_bits / (8 size), rounded), offset[s] the
+   place of its 1 << (header[s] & 31) table bytes (none when that log2 is 0) in
+   d_tables, offset[nseg] = *tables_len.  The tables lie compactly in segment
+   order in d_tables (device, 16-byte aligned, capacity bytes).  d_tables NULL
+   is a size query.  When *tables_len > capacity the call returns
+   UGPU_CAPACITY with every host output valid; d_tables then holds the tables
+   of some leading segments.  A final table has at most max(128, the smallest
+   power of two above 100 n / max_noise) bytes, which bounds a capacity without
+   a query.  UGPU_INVAL, decided before the device is touched: accuracy > 9, an
+   unknown flag, bounds that descend or pass len.  nseg == 0 gives
+   *tables_len = 0.  The device workspace for tables is bounded (256 MiB;
+   segments go in groups).  Synchronous. */
+int ugpu_index_tables(const uint8_t *dbuf, uint64_t len, const uint64_t *bounds, uint32_t nseg, uint32_t accuracy,
+                      uint32_t flags, uint8_t *header, uint32_t *zero_bits, uint64_t *offset, uint8_t *d_tables,
+                      uint64_t capacity, uint64_t *tables_len, void *stream);
+
+/* ugpu_index_tables over host inputs: packed back to back, with no separator
+   bytes, through pinned memory, in sub-batches cut between inputs as for
+   ugpu_find_batch.  Zero-length inputs are legal anywhere; ninputs == 0 gives
+   an empty result; accuracy > 9 and a NULL bufs[i] with lens[i] > 0 give
+   UGPU_INVAL.  The arrays of the result are malloc'd and freed by
+   ugpu_index_free: header and zero_bits per input, offset[ninputs + 1] into
+   tables. */
+typedef struct ugpu_index_result
+{
+  uint32_t ninputs;
+  uint32_t accuracy;
+  uint8_t *header;
+  uint32_t *zero_bits;
+  uint64_t *offset;
+  uint8_t *tables;
+} ugpu_index_result;
+int ugpu_index_batch(const uint8_t *const *bufs, const uint64_t *lens, uint32_t ninputs, uint32_t accuracy,
+                     uint32_t flags, ugpu_index_result **out);
+int ugpu_index_free(ugpu_index_result *r);
+
 /* --- synthetic corpora, generated on device --- */
 #define UGPU_GEN_WORDS 1
 #define UGPU_GEN_PLANTED 2

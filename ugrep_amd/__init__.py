@@ -12,6 +12,8 @@ from .matcher import (compile_regex, Matcher, Pattern, Records, Scanner, Stream,
                       host_plan, host_prefilter, host_tables, host_transducer, is_binary, isutf8, lines,
                       LineResult, context_lines, grep_lines, line_spans, select_lines,
                       PositionResult, columns, find_positions,
+                      IndexResult, index_batch, index_chunk, index_directory, index_inputs, index_tables,
+                      parse_index_store, write_index_store,
                       ENCODINGS, decode_input, detect_bom, find_encoded, transcode, transcode_bound,
                       grep_bool, host_newline, host_ngram, host_ngram_candidates, parse_bool_query, select_lines_bool,
                       BatchResult, find_batch, host_batch_plan, split_matches)
@@ -21,4 +23,6 @@ __all__ = ["compile_regex", "Pattern", "Matcher", "Records", "Scanner", "Stream"
            "grep_lines", "LineResult", "select_lines_bool", "parse_bool_query", "grep_bool", "host_newline",
            "host_ngram", "host_ngram_candidates", "BatchResult", "find_batch", "host_batch_plan", "split_matches",
            "columns", "find_positions", "PositionResult",
-           "detect_bom", "transcode", "transcode_bound", "decode_input", "find_encoded", "ENCODINGS"]
+           "detect_bom", "transcode", "transcode_bound", "decode_input", "find_encoded", "ENCODINGS",
+           "IndexResult", "index_batch", "index_chunk", "index_directory", "index_inputs", "index_tables",
+           "parse_index_store", "write_index_store"]

@@ -34,6 +34,8 @@ BOOL_FILES = 2
 BOOL_MAX_LISTS, BOOL_MAX_CLAUSES = 16, 64
 BATCH_ONE_SCAN = 1
 
+INDEX_IGNORE_BINARY = 1
+
 ENC_PLAIN, ENC_UTF8, ENC_UTF16BE, ENC_UTF16LE, ENC_UTF32BE, ENC_UTF32LE, ENC_LATIN1, ENC_PAGE, ENC_NULL_DATA = range(9)
 
 c_u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -63,6 +65,11 @@ class BatchResult(ctypes.Structure):
     _fields_ = [("ninputs", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("count", ctypes.c_uint64),
                 ("first", c_u64p), ("digest", c_u64p), ("dcap", c_u64p), ("newlines", c_u64p),
                 ("matching_lines", c_u64p), ("start", c_u64p), ("len", c_u32p), ("cap", c_u32p), ("line", c_u64p)]
+
+
+class IndexResult(ctypes.Structure):
+    _fields_ = [("ninputs", ctypes.c_uint32), ("accuracy", ctypes.c_uint32), ("header", c_u8p),
+                ("zero_bits", c_u32p), ("offset", c_u64p), ("tables", c_u8p)]
 
 
 class BoolClause(ctypes.Structure):
@@ -174,6 +181,13 @@ def _load():
         "ugpu_transcode_bound": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint64, P(ctypes.c_uint64)]),
         "ugpu_transcode": (ctypes.c_int, [V, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, c_u16p, V,
                                           ctypes.c_uint64, P(ctypes.c_uint64), V]),
+        "ugpu_index_chunk": (ctypes.c_uint64, []),
+        "ugpu_index_tables": (ctypes.c_int, [V, ctypes.c_uint64, c_u64p, ctypes.c_uint32, ctypes.c_uint32,
+                                             ctypes.c_uint32, c_u8p, c_u32p, c_u64p, V, ctypes.c_uint64,
+                                             P(ctypes.c_uint64), V]),
+        "ugpu_index_batch": (ctypes.c_int, [P(V), c_u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                            P(P(IndexResult))]),
+        "ugpu_index_free": (ctypes.c_int, [P(IndexResult)]),
         "ugpu_compile": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(c_u32p),
                                         P(ctypes.c_uint32)]),
         "ugpu_opc_free": (None, [c_u32p]),

@@ -1225,3 +1225,168 @@ def find_encoded(pattern, data, encoding=None, page=None, offsets=True):
     stream, as ugrep -b prints them."""
     dev, n = decode_input(data, encoding, page)
     return find_all(pattern, dev[:n], offsets=offsets)
+
+
+# ---- file indexes (ugpu_index_tables, ugpu_index_batch): ugrep-indexer's pass
+
+INDEX_MAGIC = b"UG#\x03\x00"
+INDEX_STORE = "._UG#_Store"
+
+
+class IndexResult:
+    """Per-input results of index_batch: header[i] is the record's second byte
+    (log2 of the table size, bit 7: binary), zero_bits[i] the zero bits of the
+    final table, and input i's table is tables[offset[i]:offset[i+1]]."""
+
+    def __init__(self, accuracy, header, zero_bits, offset, tables):
+        self.accuracy, self.header, self.zero_bits, self.offset, self.tables = accuracy, header, zero_bits, offset, tables
+
+    def __len__(self):
+        return len(self.header)
+
+    def table(self, i):
+        return self.tables[int(self.offset[i]):int(self.offset[i + 1])].tobytes()
+
+    def binary(self, i):
+        return bool(self.header[i] & 0x80)
+
+    def noise_percent(self, i):
+        """What ugrep-indexer -v prints for the input."""
+        size = int(self.offset[i + 1]) - int(self.offset[i])
+        return int(100.0 * int(self.zero_bits[i]) / (8 * size) + 0.5) if size else 0
+
+
+def index_chunk():
+    """ugpu_index_chunk: the bytes of an input one workgroup hashes."""
+    return int(lib.ugpu_index_chunk())
+
+
+def index_tables(dptr, length, bounds, accuracy=4, ignore_binary=False, d_tables=0, capacity=0, stream=0):
+    """ugpu_index_tables over the segments [bounds[s], bounds[s+1]) of a 16-byte
+    aligned device buffer: (header, zero_bits, offset, tables_len) with the
+    tables written to the device buffer d_tables of `capacity` bytes (0: a size
+    query).  Too small a capacity raises UgpuError (UGPU_CAPACITY) with the
+    length in its .out_len."""
+    b = np.ascontiguousarray(bounds, dtype=np.uint64)
+    nseg = b.size - 1
+    header = np.zeros(nseg + 1, np.uint8)
+    zeros = np.zeros(nseg + 1, np.uint32)
+    offset = np.zeros(nseg + 1, np.uint64)
+    total = ctypes.c_uint64()
+    rc = lib.ugpu_index_tables(ctypes.c_void_p(dptr or None), length, b.ctypes.data_as(_lib.c_u64p), nseg, accuracy,
+                               _lib.INDEX_IGNORE_BINARY if ignore_binary else 0, header.ctypes.data_as(_lib.c_u8p),
+                               zeros.ctypes.data_as(_lib.c_u32p), offset.ctypes.data_as(_lib.c_u64p),
+                               ctypes.c_void_p(d_tables or None), capacity, ctypes.byref(total), ctypes.c_void_p(stream))
+    if rc == _lib.UGPU_CAPACITY:
+        err = _lib.UgpuError(rc, lib.ugpu_last_error().decode(errors="replace"))
+        err.out_len = total.value
+        raise err
+    check(rc)
+    return header[:nseg], zeros[:nseg], offset, total.value
+
+
+def index_batch(inputs, accuracy=4, ignore_binary=False):
+    """ugpu_index_batch: the index records of a sequence of host inputs (bytes,
+    numpy or host tensors), each as ugrep-indexer -ACCURACY [-I] computes it for
+    a file of those bytes: an IndexResult."""
+    bufs = [_buffer_ptr(d) for d in inputs]
+    k = len(bufs)
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[b[0] if b[1] else None for b in bufs])
+    lens = np.array([b[1] for b in bufs], dtype=np.uint64)
+    res = ctypes.POINTER(_lib.IndexResult)()
+    check(lib.ugpu_index_batch(ptrs, lens.ctypes.data_as(_lib.c_u64p), k, accuracy,
+                               _lib.INDEX_IGNORE_BINARY if ignore_binary else 0, ctypes.byref(res)))
+    try:
+        r = res.contents
+
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dt)
+
+        offset = np.ctypeslib.as_array(r.offset, shape=(k + 1,)).copy()
+        out = IndexResult(accuracy, arr(r.header, k, np.uint8), arr(r.zero_bits, k, np.uint32), offset,
+                          arr(r.tables, int(offset[k]), np.uint8))
+    finally:
+        lib.ugpu_index_free(res)
+    del bufs
+    return out
+
+
+def _host_decoded(data):
+    """index_inputs' bytes of one input, in host memory: behind a UTF-8 BOM, or
+    converted on the device when a UTF-16/32 BOM says so."""
+    _, n, keep = _buffer_ptr(data)
+    host = keep if isinstance(keep, np.ndarray) else keep.reshape(-1).cpu().numpy().view(np.uint8)
+    enc, skip = detect_bom(host[:4].tobytes() if n else b"", n)
+    if enc in (_lib.ENC_PLAIN, _lib.ENC_UTF8):
+        return host[skip:]
+    dev, m = decode_input(host)
+    return dev[:m].cpu().numpy()
+
+
+def index_inputs(inputs, accuracy=4, ignore_binary=False):
+    """index_batch over the bytes reflex::Input delivers for each input: a UTF-8
+    BOM is dropped, UTF-16/32 with a BOM is converted (detect_bom,
+    decode_input)."""
+    return index_batch([_host_decoded(d) for d in inputs], accuracy, ignore_binary)
+
+
+def write_index_store(names, result, accuracy=None):
+    """The bytes of a ._UG#_Store (src/ugrep-indexer.cpp:1725-1745): the magic,
+    then per input the accuracy digit, the header byte, the length of the name
+    (16 bits, little endian), the name and the table.  `result` is an
+    IndexResult or a sequence of (header, table) pairs; names are str (encoded
+    as the file system does) or bytes."""
+    import os
+    if isinstance(result, IndexResult):
+        accuracy = result.accuracy if accuracy is None else accuracy
+        result = [(int(result.header[i]), result.table(i)) for i in range(len(result))]
+    if accuracy is None or not 0 <= accuracy <= 9:
+        raise ValueError("accuracy is 0..9")
+    if len(names) != len(result):
+        raise ValueError("one name per record")
+    out = [INDEX_MAGIC]
+    for name, (header, table) in zip(names, result):
+        name = (name if isinstance(name, bytes) else os.fsencode(name))[:65535]
+        size = (1 << (header & 0x1F)) if header & 0x1F else 0
+        if len(table) != size:
+            raise ValueError("table of %d bytes under header 0x%02x" % (len(table), header))
+        out += [bytes([0x30 + accuracy, header, len(name) & 0xFF, len(name) >> 8]), name, bytes(table)]
+    return b"".join(out)
+
+
+def parse_index_store(blob):
+    """The records of a ._UG#_Store: [(name bytes, accuracy, header, table bytes)]."""
+    blob = bytes(blob)
+    if blob[:5] != INDEX_MAGIC:
+        raise ValueError("not an index store")
+    out, p = [], 5
+    while p < len(blob):
+        if p + 4 > len(blob):
+            raise ValueError("truncated record")
+        acc, header = blob[p] - 0x30, blob[p + 1]
+        ln = blob[p + 2] | (blob[p + 3] << 8)
+        size = (1 << (header & 0x1F)) if header & 0x1F else 0
+        q = p + 4 + ln + size
+        if q > len(blob):
+            raise ValueError("truncated record")
+        out.append((blob[p + 4:p + 4 + ln], acc, header, blob[p + 4 + ln:q]))
+        p = q
+    return out
+
+
+def index_directory(path, accuracy=4, ignore_binary=False):
+    """Indexes the regular, non-hidden files of one directory (symbolic links
+    are skipped) and writes its ._UG#_Store, names in sorted order; returns
+    (names, IndexResult).  No recursion, archives, ignore files or incremental
+    update."""
+    import os
+    names = sorted(e.name for e in os.scandir(path)
+                   if not e.name.startswith(".") and e.is_file(follow_symlinks=False) and not e.is_symlink())
+    datas = []
+    for nm in names:
+        with open(os.path.join(path, nm), "rb") as f:
+            datas.append(f.read())
+    res = index_inputs(datas, accuracy, ignore_binary)
+    with open(os.path.join(path, INDEX_STORE), "wb") as f:
+        f.write(write_index_store(names, res))
+    return names, res
