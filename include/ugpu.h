@@ -730,9 +730,8 @@ int ugpu_transcode(const uint8_t *dbuf, uint64_t len, uint64_t start, uint32_t e
    an empty input, and a binary one under UGPU_INDEX_IGNORE_BINARY (-I), has
    log2 0 and no table.  The bytes to pass are those reflex::Input delivers
    (ugpu_detect_bom / ugpu_transcode for a file with a BOM).  Archives,
-   decompression, --check, --delete and incremental updates are not here, and
-   neither is the query (Pattern::match_hfa), which reads these tables as the
-   reference's. */
+   decompression, --check, --delete and incremental updates are not here.  The
+   query over these tables (Pattern::match_hfa) is ugpu_index_query below. */
 #define UGPU_INDEX_IGNORE_BINARY 1u
 
 /* The bytes of an input one workgroup hashes: an input of up to this many
@@ -780,6 +779,123 @@ typedef struct ugpu_index_result
 int ugpu_index_batch(const uint8_t *const *bufs, const uint64_t *lens, uint32_t ninputs, uint32_t accuracy,
                      uint32_t flags, ugpu_index_result **out);
 int ugpu_index_free(ugpu_index_result *r);
+
+/* --- the index query: which records may match ---
+   ugrep --index compiles its pattern with option h (src/ugrep.cpp:8849) into a
+   "hash finite automaton" and asks it, per record of a ._UG#_Store, whether
+   the file can match; a file that cannot is not opened.
+
+   ugpu_hfa_create replaces Pattern::gen_match_hfa, gen_match_hfa_start and
+   gen_match_hfa_transitions (lib/pattern.cpp:4641-4755).  For every DFA state
+   reachable in level + 1 bytes from the start, level 0..15, and every offset
+   in max(0, level - 7)..level, it keeps the set of hashes (indexhash,
+   include/reflex/pattern.h:1284: h' = (61 h + b) mod 2^16, the indexer's) of
+   the byte chains that begin at depth `offset` and end with the state's
+   incoming byte, and the state's successors.  A state without successors is
+   "dead", which means accept: one that accepts, has no edges, or whose lowest
+   edge leads to such a state (:4687 with next_accepting, pattern.h:740-745,
+   looks at that edge alone).  It is built from the native compiler's subset
+   DFA before minimisation (the reference's DFA is not minimised either), with
+   `flags` the UGPU_RX_* of ugpu_compile.  Assertions at a pattern's ends (the
+   reference's meta edges, which its closure skips) are dropped: a superset
+   language.  A construct the native compiler refuses gives UGPU_UNSUPPORTED
+   (message in ugpu_last_error); the caller then keeps every file.  A pattern
+   whose start state accepts or has no edges (a*) has no automaton
+   (Pattern::has_hfa false, src/ugrep.cpp:8931): every file is kept.
+   The reference truncates an automaton of more than 1024 states or 262144
+   ranges per state in the order of its states' addresses (:4695, :4748); here
+   generation stops when the 1024 state ids or 4 Mi ranges run out and every
+   entry of the last level is dead, which keeps more files and never fewer, and
+   parity is not claimed (info.truncated). */
+typedef struct ugpu_hfa ugpu_hfa;
+typedef struct ugpu_hfa_info_t
+{
+  uint32_t has_hfa;   /* 0: no automaton, every file is kept */
+  uint32_t levels;    /* levels with entries, up to 16 */
+  uint32_t states;    /* distinct states among the entries */
+  uint32_t entries;   /* (state, level) pairs */
+  uint32_t ranges;    /* hash ranges over all entries and offsets */
+  uint32_t truncated; /* cut short: looser than the reference may be */
+  uint64_t hashes;    /* hashes in those ranges */
+} ugpu_hfa_info_t;
+int ugpu_hfa_create(const char *regex, size_t len, uint32_t flags, ugpu_hfa **hfa);
+int ugpu_hfa_destroy(ugpu_hfa *hfa);
+int ugpu_hfa_info(const ugpu_hfa *hfa, ugpu_hfa_info_t *info);
+/* The flattened automaton as 32-bit words (layout: ugrep_amd/csrc/hfa.hpp):
+   export with words NULL is a size query (0 words: no automaton); import
+   checks every index and returns UGPU_INVAL for words it cannot follow. */
+int ugpu_hfa_export(const ugpu_hfa *hfa, uint32_t *words, uint64_t capacity, uint64_t *nwords);
+int ugpu_hfa_import(const uint32_t *words, uint64_t nwords, ugpu_hfa **hfa);
+
+/* Pattern::match_hfa and match_hfa_transitions (lib/pattern.cpp:4757-4815)
+   over one table of `size` bytes (a power of two up to 65536), host only:
+   *keep = 1 when the file may match.  Levels run in order with two visit sets
+   that alternate by level & 1 and are never cleared (a state seen at an
+   earlier depth of the same parity stays visited); level 0 tests every entry.
+   A visited entry passes an offset when some hash h of that set has bit
+   level - offset clear in table[h & (size - 1)].  Offsets are tried in
+   ascending order up to the first that fails; each one that passes marks the
+   entry's successors for the next level, so an entry propagates iff its first
+   offset passes, and a dead entry whose first offset passes ends the query
+   with keep.  A level on which no entry passes all its offsets ends it with
+   skip.  Without an automaton *keep = 1. */
+int ugpu_hfa_match_host(const ugpu_hfa *hfa, const uint8_t *table, uint64_t size, int *keep);
+/* The decision per record (see ugpu_index_query) on the host, tables in host
+   memory: the fallback without a device.  Without an automaton every byte of
+   keep is 1, whatever the headers say. */
+int ugpu_hfa_query_host(const ugpu_hfa *hfa, const uint8_t *tables, const uint8_t *header, const uint64_t *offset,
+                        uint32_t nrec, uint32_t flags, uint8_t *keep);
+
+/* The decision per record (src/ugrep.cpp:10060-10099), on the device.  header,
+   offset (nrec + 1 values) and d_tables lie as ugpu_index_tables leaves them
+   (header and offset in host memory, d_tables a device buffer).  With
+   b = header[s]: b & 0x80 under UGPU_QUERY_IGNORE_BINARY (-I) skips; b & 0x60
+   (an archive or a compressed file) without UGPU_QUERY_DECOMPRESS (-z) skips;
+   a table (b & 0x1F != 0) keeps iff the automaton does; no table keeps iff
+   b & 0x80.  keep (host, nrec bytes) gets 0 = skip, 1 = keep.  Without an
+   automaton every byte is 1 and nothing is launched.  A table must lie inside
+   [0, offset[nrec]) at its offset, else UGPU_INVAL before the device is touched.
+   One wave walks one record; a table of up to ugpu_index_query_lds() bytes is
+   staged in LDS first, a larger one is probed in global memory (the
+   UGPU_QUERY_FORCE_* flags pin either way, for tests and measurements).
+   The automaton's words are uploaded when the pooled workspace that serves the
+   call last served another ugpu_hfa (a copy per workspace, not per ugpu_hfa).
+   Synchronous. */
+#define UGPU_QUERY_IGNORE_BINARY 1u
+#define UGPU_QUERY_DECOMPRESS 2u
+#define UGPU_QUERY_FORCE_LDS 0x100u    /* stage every table (up to 65536 bytes) */
+#define UGPU_QUERY_FORCE_GLOBAL 0x200u /* stage none */
+int ugpu_index_query(const ugpu_hfa *hfa, const uint8_t *d_tables, const uint8_t *header,
+                     const uint64_t *offset, uint32_t nrec, uint32_t flags, uint8_t *keep, void *stream);
+uint32_t ugpu_index_query_lds(void);
+/* ugpu_index_query over tables in host memory, compact as ugpu_index_batch
+   returns them (offsets ascending): they go through pinned memory in
+   sub-batches cut between records. */
+int ugpu_index_query_records(const ugpu_hfa *hfa, const uint8_t *tables, const uint8_t *header, const uint64_t *offset,
+                             uint32_t nrec, uint32_t flags, uint8_t *keep);
+/* The device time (hipEvents around the kernels, ms) of this thread's last
+   ugpu_index_query, ugpu_index_query_records or ugpu_index_query_store. */
+int ugpu_index_query_kernel_ms(float *ms);
+
+/* ugpu_index_query over nblobs index stores as read from disk (host memory):
+   the records are parsed on the host (the magic, then per record the accuracy
+   digit, the header byte, the name's length in 16 bits, the name, the table),
+   the tables go through pinned memory in sub-batches and the result holds one
+   keep byte per record with its name's place: name_blob[i], name_off[i],
+   name_len[i].  UGPU_INVAL for a blob without the magic or with a cut record.
+   Freed by ugpu_query_free. */
+typedef struct ugpu_query_result
+{
+  uint32_t nrec;
+  uint8_t *keep;
+  uint8_t *header;
+  uint32_t *name_blob;
+  uint64_t *name_off;
+  uint32_t *name_len;
+} ugpu_query_result;
+int ugpu_index_query_store(const ugpu_hfa *hfa, const uint8_t *const *blobs, const uint64_t *lens, uint32_t nblobs,
+                           uint32_t flags, ugpu_query_result **out);
+int ugpu_query_free(ugpu_query_result *r);
 
 /* --- synthetic corpora, generated on device --- */
 #define UGPU_GEN_WORDS 1

@@ -14,6 +14,7 @@ from .matcher import (compile_regex, Matcher, Pattern, Records, Scanner, Stream,
                       PositionResult, columns, find_positions,
                       IndexResult, index_batch, index_chunk, index_directory, index_inputs, index_tables,
                       parse_index_store, write_index_store,
+                      IndexQuery, find_indexed, query_index_store,
                       ENCODINGS, decode_input, detect_bom, find_encoded, transcode, transcode_bound,
                       grep_bool, host_newline, host_ngram, host_ngram_candidates, parse_bool_query, select_lines_bool,
                       BatchResult, find_batch, host_batch_plan, split_matches)
@@ -25,4 +26,4 @@ __all__ = ["compile_regex", "Pattern", "Matcher", "Records", "Scanner", "Stream"
            "columns", "find_positions", "PositionResult",
            "detect_bom", "transcode", "transcode_bound", "decode_input", "find_encoded", "ENCODINGS",
            "IndexResult", "index_batch", "index_chunk", "index_directory", "index_inputs", "index_tables",
-           "parse_index_store", "write_index_store"]
+           "parse_index_store", "write_index_store", "IndexQuery", "find_indexed", "query_index_store"]

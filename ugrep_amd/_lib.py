@@ -35,6 +35,7 @@ BOOL_MAX_LISTS, BOOL_MAX_CLAUSES = 16, 64
 BATCH_ONE_SCAN = 1
 
 INDEX_IGNORE_BINARY = 1
+QUERY_IGNORE_BINARY, QUERY_DECOMPRESS, QUERY_FORCE_LDS, QUERY_FORCE_GLOBAL = 1, 2, 0x100, 0x200
 
 ENC_PLAIN, ENC_UTF8, ENC_UTF16BE, ENC_UTF16LE, ENC_UTF32BE, ENC_UTF32LE, ENC_LATIN1, ENC_PAGE, ENC_NULL_DATA = range(9)
 
@@ -70,6 +71,16 @@ class BatchResult(ctypes.Structure):
 class IndexResult(ctypes.Structure):
     _fields_ = [("ninputs", ctypes.c_uint32), ("accuracy", ctypes.c_uint32), ("header", c_u8p),
                 ("zero_bits", c_u32p), ("offset", c_u64p), ("tables", c_u8p)]
+
+
+class HfaInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("has_hfa", "levels", "states", "entries", "ranges", "truncated")] + [
+        ("hashes", ctypes.c_uint64)]
+
+
+class QueryResult(ctypes.Structure):
+    _fields_ = [("nrec", ctypes.c_uint32), ("keep", c_u8p), ("header", c_u8p), ("name_blob", c_u32p),
+                ("name_off", c_u64p), ("name_len", c_u32p)]
 
 
 class BoolClause(ctypes.Structure):
@@ -188,6 +199,21 @@ def _load():
         "ugpu_index_batch": (ctypes.c_int, [P(V), c_u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
                                             P(P(IndexResult))]),
         "ugpu_index_free": (ctypes.c_int, [P(IndexResult)]),
+        "ugpu_hfa_create": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(V)]),
+        "ugpu_hfa_destroy": (ctypes.c_int, [V]),
+        "ugpu_hfa_info": (ctypes.c_int, [V, P(HfaInfo)]),
+        "ugpu_hfa_export": (ctypes.c_int, [V, c_u32p, ctypes.c_uint64, P(ctypes.c_uint64)]),
+        "ugpu_hfa_import": (ctypes.c_int, [c_u32p, ctypes.c_uint64, P(V)]),
+        "ugpu_hfa_match_host": (ctypes.c_int, [V, c_u8p, ctypes.c_uint64, P(ctypes.c_int)]),
+        "ugpu_index_query": (ctypes.c_int, [V, V, c_u8p, c_u64p, ctypes.c_uint32, ctypes.c_uint32, c_u8p, V]),
+        "ugpu_index_query_lds": (ctypes.c_uint32, []),
+        "ugpu_hfa_query_host": (ctypes.c_int, [V, c_u8p, c_u8p, c_u64p, ctypes.c_uint32, ctypes.c_uint32, c_u8p]),
+        "ugpu_index_query_records": (ctypes.c_int, [V, c_u8p, c_u8p, c_u64p, ctypes.c_uint32, ctypes.c_uint32,
+                                                    c_u8p]),
+        "ugpu_index_query_kernel_ms": (ctypes.c_int, [P(ctypes.c_float)]),
+        "ugpu_index_query_store": (ctypes.c_int, [V, P(V), c_u64p, ctypes.c_uint32, ctypes.c_uint32,
+                                                  P(P(QueryResult))]),
+        "ugpu_query_free": (ctypes.c_int, [P(QueryResult)]),
         "ugpu_compile": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, P(c_u32p),
                                         P(ctypes.c_uint32)]),
         "ugpu_opc_free": (None, [c_u32p]),

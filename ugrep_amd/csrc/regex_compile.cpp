@@ -55,6 +55,7 @@
 
 #include "ugpu.h"
 #include "ctx_bits.hpp"
+#include "subset_dfa.hpp"
 
 using ugpu::CTX_BOL;
 using ugpu::CTX_BW;
@@ -2544,9 +2545,9 @@ bool rx_assertion_groups(const std::string &r, std::string &rewritten, std::vect
   return changed;
 }
 
-// opcode words of rx; accept: the accept index of each top-level alternative
-// (empty: 1, 2, ...)
-std::vector<uint32_t> compile_words(const std::string &rx, uint32_t flags, const std::vector<int> &accept)
+// the subset DFA of rx (start state 1, not minimised); accept: the accept index
+// of each top-level alternative (empty: 1, 2, ...)
+Dfa subset_dfa_of(const std::string &rx, uint32_t flags, const std::vector<int> &accept)
 {
   Tree tree;
   Parser parser(rx, flags, tree);
@@ -2565,12 +2566,60 @@ std::vector<uint32_t> compile_words(const std::string &rx, uint32_t flags, const
     if (info.nullable)
       Glushkov::merge(start, std::vector<int>{end});
   }
-  Dfa d = subsets(g, start);
-  Dfa m = unfold_gaps(minimize(d, 1));
+  return subsets(g, start);
+}
+
+// opcode words of rx
+std::vector<uint32_t> compile_words(const std::string &rx, uint32_t flags, const std::vector<int> &accept)
+{
+  Dfa m = unfold_gaps(minimize(subset_dfa_of(rx, flags, accept), 1));
   return encode(m);
 }
 
 }  // namespace
+
+// The hook of hfa.cpp (subset_dfa.hpp): the subset DFA before minimize(), as
+// the reference's HFA is built from its unminimised DFA.  A state accepts when
+// it does in any context, i.e. with the assertions at the pattern's ends taken
+// away (a superset language).  Patterns are rewritten as ugpu_compile does.
+int ugpu::subset_dfa(const char *regex, size_t len, uint32_t flags, SubsetDfa &out)
+{
+  try
+  {
+    std::string rx(regex ? regex : "", len);
+    Dfa d;
+    try
+    {
+      d = subset_dfa_of(rx, flags, std::vector<int>());
+    }
+    catch (const CompileError &e)
+    {
+      std::string r2;
+      std::vector<int> accept;
+      if (e.code != UGPU_UNSUPPORTED || (flags & UGPU_RX_FIXED) || !rx_assertion_groups(rx, r2, accept))
+        throw;
+      d = subset_dfa_of(r2, flags, accept);
+    }
+    out.next.swap(d.next);
+    out.accepting.assign(out.next.size(), 0);
+    for (size_t s = 0; s < out.next.size(); ++s)
+      for (uint32_t a : d.cx[s])
+        if (a)
+          out.accepting[s] = 1;
+    g_compile_error.clear();
+    return UGPU_OK;
+  }
+  catch (const CompileError &e)
+  {
+    g_compile_error = e.msg;
+    return e.code;
+  }
+  catch (const std::bad_alloc &)
+  {
+    g_compile_error = "out of memory";
+    return UGPU_NOMEM;
+  }
+}
 
 extern "C" {
 

@@ -1390,3 +1390,205 @@ def index_directory(path, accuracy=4, ignore_binary=False):
     with open(os.path.join(path, INDEX_STORE), "wb") as f:
         f.write(write_index_store(names, res))
     return names, res
+
+
+# --- the index query: which records of an index may match a pattern ---
+
+_DEVICES = []
+
+
+def _device_visible():
+    if not _DEVICES:
+        n = ctypes.c_int()
+        _DEVICES.append(lib.ugpu_device_count(ctypes.byref(n)) == _lib.UGPU_OK and n.value > 0)
+    return _DEVICES[0]
+
+
+class IndexQuery:
+    """The hash finite automaton of a pattern (ugpu_hfa_create, what ugrep
+    --index builds with Pattern option h) and its query over index tables.
+    Unsupported is raised for a pattern the native compiler refuses: keep every
+    file then.  `words`: a flattened automaton (ugpu_hfa_import) in place of a
+    pattern."""
+
+    def __init__(self, pattern=None, fixed=False, icase=False, words=None):
+        h = ctypes.c_void_p()
+        if words is not None:
+            w = np.ascontiguousarray(words, dtype=np.uint32)
+            check(lib.ugpu_hfa_import(w.ctypes.data_as(_lib.c_u32p), w.size, ctypes.byref(h)))
+        else:
+            rx = pattern.encode("utf-8") if isinstance(pattern, str) else bytes(pattern)
+            check(lib.ugpu_hfa_create(rx, len(rx), (RX_FIXED if fixed else 0) | (RX_ICASE if icase else 0),
+                                      ctypes.byref(h)))
+        self._h = h
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def info(self):
+        """dict of ugpu_hfa_info: has_hfa, levels, states, entries, ranges, truncated, hashes."""
+        i = _lib.HfaInfo()
+        check(lib.ugpu_hfa_info(self._h, ctypes.byref(i)))
+        return {n: int(getattr(i, n)) for n, _ in _lib.HfaInfo._fields_}
+
+    def words(self):
+        """The flattened automaton (ugpu_hfa_export; empty: no automaton)."""
+        n = ctypes.c_uint64()
+        check(lib.ugpu_hfa_export(self._h, None, 0, ctypes.byref(n)))
+        w = np.zeros(max(n.value, 1), np.uint32)
+        check(lib.ugpu_hfa_export(self._h, w.ctypes.data_as(_lib.c_u32p), w.size, ctypes.byref(n)))
+        return w[:n.value]
+
+    def match_host(self, table):
+        """ugpu_hfa_match_host: whether a file with this index table may match."""
+        t = np.frombuffer(bytes(table), np.uint8) if not isinstance(table, np.ndarray) else np.ascontiguousarray(table)
+        keep = ctypes.c_int()
+        check(lib.ugpu_hfa_match_host(self._h, t.ctypes.data_as(_lib.c_u8p), t.size, ctypes.byref(keep)))
+        return bool(keep.value)
+
+    def keep_host(self, header, table, ignore_binary=False, decompress=False):
+        """The decision for one record on the host (src/ugrep.cpp:10060-10099)."""
+        if not self.info["has_hfa"]:
+            return True  # the index is off for such a pattern, whatever the header says (src/ugrep.cpp:8931)
+        if (header & 0x80 and ignore_binary) or (header & 0x60 and not decompress):
+            return False
+        return self.match_host(table) if header & 0x1F else bool(header & 0x80)
+
+    def query(self, result_or_tables, ignore_binary=False, decompress=False, force=None, device=None):
+        """One keep flag (numpy bool) per record of an IndexResult, of
+        parse_index_store's output (a list of (name, accuracy, header, table)),
+        both through ugpu_index_query_records, or of the device form (d_tables,
+        header, offset) as index_tables leaves it (ugpu_index_query).  force:
+        "lds" or "global" pins where the kernel reads the tables.  device:
+        False runs the host evaluator (ugpu_hfa_query_host) over host tables,
+        which is also what None does when no device is visible."""
+        flags = ((_lib.QUERY_IGNORE_BINARY if ignore_binary else 0) | (_lib.QUERY_DECOMPRESS if decompress else 0) |
+                 {None: 0, "lds": _lib.QUERY_FORCE_LDS, "global": _lib.QUERY_FORCE_GLOBAL}[force])
+        r = result_or_tables
+        on_host = isinstance(r, (IndexResult, list))
+        if isinstance(r, IndexResult):
+            tables, header, offset = r.tables, r.header, r.offset
+        elif isinstance(r, list):
+            header = np.array([h for _, _, h, _ in r], dtype=np.uint8)
+            offset = np.concatenate([[0], np.cumsum([len(t) for _, _, _, t in r])]).astype(np.uint64)
+            tables = np.frombuffer(b"".join(bytes(t) for _, _, _, t in r), np.uint8)
+        else:
+            tables, header, offset = r
+        header = np.ascontiguousarray(header, dtype=np.uint8)
+        offset = np.ascontiguousarray(offset, dtype=np.uint64)
+        n = header.size
+        if offset.size != n + 1:
+            raise ValueError("offset holds one value per record and the tables' length")
+        keep = np.zeros(n + 1, np.uint8)
+        hp, op, kp = header.ctypes.data_as(_lib.c_u8p), offset.ctypes.data_as(_lib.c_u64p), keep.ctypes.data_as(_lib.c_u8p)
+        if on_host:
+            tables = np.ascontiguousarray(tables, dtype=np.uint8)
+            if device is None:
+                device = _device_visible()
+            fn = lib.ugpu_index_query_records if device else lib.ugpu_hfa_query_host
+            check(fn(self._h, tables.ctypes.data_as(_lib.c_u8p), hp, op, n, flags, kp))
+        else:
+            check(lib.ugpu_index_query(self._h, ctypes.c_void_p(tables or None), hp, op, n, flags, kp, None))
+        return keep[:n].astype(bool)
+
+    @staticmethod
+    def kernel_ms():
+        """ugpu_index_query_kernel_ms: the device time of this thread's last query."""
+        ms = ctypes.c_float()
+        check(lib.ugpu_index_query_kernel_ms(ctypes.byref(ms)))
+        return ms.value
+
+    def _query_store(self, blobs, flags):
+        """(keep, [(blob index, name bytes)]) over store blobs."""
+        blobs = [bytes(b) for b in blobs]
+        k = len(blobs)
+        ptrs = (ctypes.c_void_p * max(k, 1))(*[ctypes.cast(ctypes.c_char_p(b), ctypes.c_void_p) for b in blobs])
+        lens = np.array([len(b) for b in blobs], dtype=np.uint64)
+        res = ctypes.POINTER(_lib.QueryResult)()
+        check(lib.ugpu_index_query_store(self._h, ptrs, lens.ctypes.data_as(_lib.c_u64p), k, flags, ctypes.byref(res)))
+        try:
+            r = res.contents
+            n = r.nrec
+            keep = np.ctypeslib.as_array(r.keep, shape=(n,)).astype(bool) if n else np.zeros(0, bool)
+            names = [(int(r.name_blob[i]), blobs[r.name_blob[i]][r.name_off[i]:r.name_off[i] + r.name_len[i]])
+                     for i in range(n)]
+        finally:
+            lib.ugpu_query_free(res)
+        return keep, names
+
+    def close(self):
+        if self._h:
+            lib.ugpu_hfa_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def query_index_store(path_or_blob, pattern, fixed=False, icase=False, ignore_binary=False, decompress=False):
+    """ugpu_index_query_store over one ._UG#_Store (a path, or its bytes):
+    (names, keep), the records' names as bytes in the store's order and one
+    bool each.  A pattern the native compiler refuses keeps every record."""
+    if isinstance(path_or_blob, (bytes, bytearray, memoryview)):
+        blob = bytes(path_or_blob)
+    else:
+        with open(path_or_blob, "rb") as f:
+            blob = f.read()
+    flags = (_lib.QUERY_IGNORE_BINARY if ignore_binary else 0) | (_lib.QUERY_DECOMPRESS if decompress else 0)
+    try:
+        q = pattern if isinstance(pattern, IndexQuery) else IndexQuery(pattern, fixed, icase)
+    except _lib.Unsupported:
+        names = [p[0] for p in parse_index_store(blob)]
+        return names, np.ones(len(names), bool)
+    keep, names = q._query_store([blob], flags)
+    return [nm for _, nm in names], keep
+
+
+def find_indexed(pattern, inputs, index=None, fixed=False, icase=False, accuracy=4, offsets=True):
+    """Index, query, scan the survivors: find_batch(Pattern(compile_regex(
+    pattern)), inputs) computed over only the inputs whose index record may
+    match.  index: an IndexResult of the inputs (index_batch is run when None).
+    Returns a BatchResult equal to find_batch's over all inputs (a skipped
+    input has no match, so its records are none), with .kept, one bool per
+    input: whether it was scanned.  The inputs are host memory, as for
+    find_batch.  A skipped input is neither packed, uploaded nor scanned; its
+    bytes are still read once on the host to count its newlines, only so that
+    .newlines equals find_batch's."""
+    inputs = list(inputs)
+    if index is None:
+        index = index_batch(inputs, accuracy)
+    if len(index) != len(inputs):
+        raise ValueError("one index record per input")
+    try:
+        keep = IndexQuery(pattern, fixed, icase).query(index)
+    except _lib.Unsupported:
+        keep = np.ones(len(inputs), bool)
+    pat = Pattern(compile_regex(pattern, fixed, icase))
+    kept = [i for i in range(len(inputs)) if keep[i]]
+    sub = find_batch(pat, [inputs[i] for i in kept], offsets)
+    k = len(inputs)
+    count = np.zeros(k, np.uint64)
+    digest, dcap = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+    newlines, mlines = np.zeros(k, np.uint64), np.zeros(k, np.uint64)
+    for i in range(k):
+        if not keep[i]:
+            _, n, hold = _buffer_ptr(inputs[i])
+            if not isinstance(hold, np.ndarray):
+                if hold.is_cuda:
+                    raise TypeError("find_indexed takes host inputs, as find_batch does")
+                hold = hold.reshape(-1).numpy().view(np.uint8)
+            newlines[i] = np.count_nonzero(hold[:n] == 10)
+    for j, i in enumerate(kept):
+        count[i] = sub.first[j + 1] - sub.first[j]
+        digest[i], dcap[i], newlines[i], mlines[i] = sub.digest[j], sub.dcap[j], sub.newlines[j], sub.matching_lines[j]
+    first = np.concatenate([[0], np.cumsum(count)]).astype(np.uint64)
+    out = BatchResult(sub.one_scan, sub.count, first, digest, dcap, newlines, mlines)
+    if offsets:  # (the kept inputs' records are already in input order)
+        out.start, out.length, out.cap, out.line = sub.start, sub.length, sub.cap, sub.line
+    out.kept = keep
+    return out
